@@ -5,12 +5,18 @@ effect programs (property mutation) + dirty diff + scene-group fan-out
 (NFCScheduleModule::Execute + NFCKernelModule::Execute + NFCSceneAOIModule fan-out), and the
 consumer's nfk_outputs_get (the frame's dense event / message ranks) every frame.
 
-The default line (config[1]) also carries "host_calls": the same world with game logic between
-frames (5 % of the entities get a SetProperty, 1/64 an AddSchedule / RemoveSchedule call, every
-frame), timed the same way, with the host milliseconds per frame of queueing the calls and of
-nfk_execute's host preparation.
+A plain run sets the world up, warms up, times K frames and prints the headline line (metric,
+value, ms_per_step, the workload and the last frame's event counts); --dump-outputs DIR also
+writes what the last timed frame produced.  Everything else is behind --full: a second pass of K
+frames with HIP events around every kernel (per-kernel times, roofline), the reference's own
+modules as cpu_baseline, short legs of the other configs, the C++ plugin and drop-in adapter
+frames, and (config[1]) "host_calls": the same world with game logic between frames (5 % of the
+entities get a SetProperty, 1/64 an AddSchedule / RemoveSchedule call, every frame), timed the
+same way, with the host milliseconds per frame of queueing the calls and of nfk_execute's host
+preparation.  The legs whose frames take host milliseconds time at most --leg-steps frames (20).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]      (N > 1: bench.py starts the N ranks itself)
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR]
+                                                  (N > 1: bench.py starts the N ranks itself)
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N   (one rank per GPU)
 
 Scenes shard naturally: rank r owns scene r+1 with its own 1M entities (weak scaling, no
@@ -57,6 +63,19 @@ def parse():
     p.add_argument("--groups", type=int, default=4096)
     p.add_argument("--players-per-group", type=int, default=8)
     p.add_argument("--tick-ms", type=int, default=100)
+    p.add_argument("--full", action="store_true",
+                   help="after the headline frames also run everything else the benchmark measures: the per-kernel "
+                        "HIP-event pass and roofline, and (config[1], 1 GPU) the host_calls, plugin_frame, "
+                        "cpu_baseline, other-config and adapter_frame legs, each with its own auto/off switch below; "
+                        "without it a run sets up, warms up, times --steps frames and prints the headline line")
+    p.add_argument("--leg-steps", type=int, default=20,
+                   help="--full: the legs beside the headline (host_calls, plugin_frame, the other configs, "
+                        "adapter_frame), whose frames take host milliseconds, time at most this many frames after "
+                        "at most this many untimed ones, however many --steps the headline times")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed frames write what the last of them produced (its events, fired heartbeats "
+                        "and recipient lists, and the property state it left) as DIR/<name>.npy in float64, at most "
+                        "64 MB in all (larger arrays as a fixed seeded sample)")
     p.add_argument("--cpu-baseline", choices=["auto", "off"], default="auto")
     p.add_argument("--cpu-sample", type=int, default=4096, help="entities in the CPU baseline sample (whole groups)")
     p.add_argument("--cpu-seconds", type=float, default=15.0)
@@ -77,7 +96,7 @@ def parse():
     p.add_argument("--adapter-frame", choices=["auto", "off"], default="auto",
                    help="config[1], 1 GPU: also time the drop-in path — the reference-side plugin "
                         "(integration/NFGPUKernelPlugin.cpp) inside the reference's own kernel / AOI / schedule "
-                        "modules (tests/cpp/_ref/adapter_bench) — at config[1] and at config[0]")
+                        "modules (oracle/_ref/adapter_bench) — at config[1] and at config[0]")
     p.add_argument("--config", type=int, default=1, choices=[0, 1, 3, 4],
                    help="BASELINE config: 0 = Tutorial3 at 10k NPCs (the reference's CPU case), "
                         "1 = 1M entities/GPU (the metric's configuration; with --gpus > 1 "
@@ -147,6 +166,56 @@ def cpu_baseline(args):
                       f"NFIKernelModule::Get/SetProperty*, the window's SetProperty and schedule calls, a "
                       f"property-event consumer on the AOI module's GetBroadCastObject lists: {r['msgs']} "
                       f"recipients), single thread, {r['seconds']:.1f} s"}
+
+
+DUMP_BYTES = 60 << 20   # --dump-outputs: all files together stay under 64 MB
+DUMP_SEED = 20260
+
+
+def dump_outputs(path, m, rank=0):
+    """--dump-outputs: what the last timed frame handed its consumer (nfk_read_*: the property and
+    record events, the fired heartbeats, the fan-out's message offsets and recipients, entities as
+    object indices) and the int / float property state it left, one float64 DIR/<name>.npy each.
+    Property values are decoded by their property's type (int64 or f64 bits; an int64 beyond 2^53
+    rounds); record cells and object halves are written as their two 32-bit words.  If everything together
+    is over DUMP_BYTES, every array longer than its even share is cut to a sample of that many
+    elements, in order, drawn with a fixed seed (the same indices for the same length).  An array
+    the frame left empty is not written."""
+    t = m.read_tick()
+    t.pop("summary")
+    arrs = {}
+    is_int = t["ev_pid"] < m.n_int
+    for k in ("ev_old", "ev_new"):
+        raw = t.pop(k)
+        arrs[k] = np.where(is_int, raw.view(np.int64).astype(np.float64), raw.view(np.float64))
+    # (a record event's cell has its column's type: its raw bits, like an object value's halves, as two words)
+    for k in ("re_old", "re_new", "ev_oldh", "ev_newh"):
+        if k in t:
+            raw = t.pop(k)
+            arrs[k + "_lo"] = (raw & np.uint64(0xFFFFFFFF)).astype(np.float64)
+            arrs[k + "_hi"] = (raw >> np.uint64(32)).astype(np.float64)
+    for k, v in t.items():
+        arrs[k] = v.astype(np.float64)
+    for pid in range(m.n_int + m.n_flt):
+        arrs[f"prop_{pid:02d}"] = m.read_prop(pid).astype(np.float64)
+    if sum(a.nbytes for a in arrs.values()) > DUMP_BYTES:
+        share = DUMP_BYTES // 8 // len(arrs)
+        for k, a in arrs.items():
+            if len(a) > share:
+                idx = np.sort(np.random.default_rng(DUMP_SEED).choice(len(a), share, replace=False))
+                arrs[k] = a[idx]
+    os.makedirs(path, exist_ok=True)
+    for k, a in arrs.items():
+        if len(a) == 0:   # (nothing of this kind in the frame, e.g. record events in a world without records)
+            continue
+        np.save(os.path.join(path, k + (f"_rank{rank}" if rank else "") + ".npy"), np.ascontiguousarray(a))
+
+
+def leg_args(args):
+    """--full: the arguments of the legs beside the headline: --steps and --warmup held to --leg-steps."""
+    leg = argparse.Namespace(**vars(args))
+    leg.steps, leg.warmup = min(args.steps, args.leg_steps), min(args.warmup, args.leg_steps)
+    return leg
 
 
 class RowQueue:
@@ -345,8 +414,8 @@ def main():
     # (minutes of single-threaded host work) while this process runs its GPU legs; it touches the GPU
     # only when told to go, after them
     adapter = None
-    if world == 1 and args.config == 1 and args.adapter_frame == "auto" and not args.self_migrate:
-        adapter = AdapterLeg(args)
+    if args.full and world == 1 and args.config == 1 and args.adapter_frame == "auto" and not args.self_migrate:
+        adapter = AdapterLeg(leg_args(args))
     import torch
     import torch.distributed as dist
 
@@ -456,17 +525,20 @@ def main():
         print(json.dumps({"rank": rank, "host_ms_per_frame": {k: 1000 * v / args.steps for k, v in trace.items()},
                           "frame_ms": 1000 * elapsed / args.steps}), file=sys.stderr, flush=True)
     s = m.summary()
-    # ... then the same number of frames again with HIP events around every kernel, for the
-    # per-kernel durations and algorithmic bytes of the roofline
-    m.reset_kernel_times()
-    m.set_profiling(True)
-    for _ in range(args.steps):
-        frame()
-    m.set_profiling(False)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, m, rank)
+    if args.full:
+        # ... then the same number of frames again with HIP events around every kernel, for the
+        # per-kernel durations and algorithmic bytes of the roofline
+        m.reset_kernel_times()
+        m.set_profiling(True)
+        for _ in range(args.steps):
+            frame()
+        m.set_profiling(False)
     moved_here = list(mig.moved()) if mig else [0, 0]
     if mig:
         mig.finish()
-    ms, nl, byts = m.kernel_times()
+    kernel_times = m.kernel_times() if args.full else None
     el = torch.tensor([elapsed], dtype=torch.float64, device=dev if args.backend == "nccl" else "cpu")
     moved = torch.tensor(moved_here, dtype=torch.int64, device=dev if args.backend == "nccl" else "cpu")
     if world > 1:
@@ -475,7 +547,56 @@ def main():
     elapsed = float(el.item())
     moved = [int(x) for x in moved.tolist()]
     m.close()
+    value = world * args.entities * args.steps / elapsed
 
+    if args.config == 1:
+        rehearsal = ("one-rank rehearsal of config[2]'s migration path (rows sent to the same rank): "
+                     if args.self_migrate and world == 1 else "")
+        wl_name = rehearsal + ((f"BASELINE config[2]: {world} scene shards (scene r+1 on GPU r), "
+                                f"{args.migrate} SwitchScene migrations per rank every {args.migrate_every} "
+                                f"frames into the next shard (state rows over "
+                                f"{'RCCL' if args.backend == 'nccl' else 'gloo'} all_to_all); per GPU: ")
+                               if migrating else "BASELINE config[1]: ") + (
+            f"{args.entities} NPC/Player entities per GPU in one scene, "
+            f"{args.groups} groups x {args.entities // args.groups}, "
+            f"{args.players_per_group} players/group, heartbeats HPRegen 1s/MPRegen 2s/"
+            f"Move 0.1s/Patrol 3s/Poison 0.5s, {args.tick_ms} ms frames")
+    else:
+        wl_name = CONFIG_NAMES[args.config]
+    out = {
+        "metric": METRIC, "value": value, "unit": "entity-ticks/s", "n_gpus": world, "steps": args.steps,
+        "warmup": warmup, "ms_per_step": 1000.0 * elapsed / args.steps, "higher_is_better": True,
+        "scaling": "weak", "vs_baseline": None, "dtype": "int64/f64", "data": "synthetic",
+        "config": {"workload": wl_name,
+                   "entities_per_gpu": args.entities, "groups": args.groups,
+                   "players_per_group": args.players_per_group, "parallelism": f"scene-shard x{world}",
+                   "migrations_per_rank_per_frame": args.migrate / args.migrate_every if migrating else 0},
+        "migrations": {"out": moved[0], "in": moved[1], "backend": args.backend,
+                       "exchange": "C++ SceneShard (RCCL side communicator for tickets, ncclSend/Recv rows)"
+                       if shard_impl == "cpp" else "noahgameframe_amd/shard.py (process group)"}
+        if migrating else None,
+        "per_frame": {"prop_events": s["n_prop_events"], "rec_events": s["n_rec_events"], "fired": s["n_fired"],
+                      "msgs": s["n_msgs"]},
+    }
+    # what the timed frame produces for the fan-out: the recipient runs per tile; each event's message
+    # offset is counted on the device when a consumer reads the frame (k_counted_moff), not in it
+    out["per_frame"]["message_offsets"] = ("produced at read time by k_counted_moff (nfk_outputs_get / nfk_read_*), "
+                                           "outside the timed frame; the headline loop's nfk_outputs_get builds "
+                                           "the dense ranks")
+    if args.full:
+        kernel_figures(args, out, s, kernel_times, migrating)
+        full_legs(args, out, rank, world, adapter, t_start, torch, kernel, workload)
+    if rank == 0:
+        print(json.dumps(out), flush=True)
+    if world > 1:
+        dist.destroy_process_group()
+
+
+def kernel_figures(args, out, s, kernel_times, migrating):
+    """--full: the per-kernel durations of the HIP-event pass and the dominant kernel's roofline,
+    added to the result line."""
+    ms, nl, byts = kernel_times
+    elapsed = out["ms_per_step"] * 1e-3 * args.steps
     # per-kernel averages over the timed region (HIP events on the world's stream)
     kern = {}
     for i, name in enumerate(KNAMES):
@@ -522,44 +643,14 @@ def main():
         except Exception:
             ceiling = None
     total_alg = sum(v["alg_bytes_per_launch"] or 0 for v in kern.values())
-    value = world * args.entities * args.steps / elapsed
-
-    if args.config == 1:
-        rehearsal = ("one-rank rehearsal of config[2]'s migration path (rows sent to the same rank): "
-                     if args.self_migrate and world == 1 else "")
-        wl_name = rehearsal + ((f"BASELINE config[2]: {world} scene shards (scene r+1 on GPU r), "
-                                f"{args.migrate} SwitchScene migrations per rank every {args.migrate_every} "
-                                f"frames into the next shard (state rows over "
-                                f"{'RCCL' if args.backend == 'nccl' else 'gloo'} all_to_all); per GPU: ")
-                               if migrating else "BASELINE config[1]: ") + (
-            f"{args.entities} NPC/Player entities per GPU in one scene, "
-            f"{args.groups} groups x {args.entities // args.groups}, "
-            f"{args.players_per_group} players/group, heartbeats HPRegen 1s/MPRegen 2s/"
-            f"Move 0.1s/Patrol 3s/Poison 0.5s, {args.tick_ms} ms frames")
-    else:
-        wl_name = CONFIG_NAMES[args.config]
-    out = {
-        "metric": METRIC, "value": value, "unit": "entity-ticks/s", "n_gpus": world, "steps": args.steps,
-        "warmup": warmup, "ms_per_step": 1000.0 * elapsed / args.steps, "higher_is_better": True,
-        "scaling": "weak", "vs_baseline": None, "dtype": "int64/f64", "data": "synthetic",
-        "config": {"workload": wl_name,
-                   "entities_per_gpu": args.entities, "groups": args.groups,
-                   "players_per_group": args.players_per_group, "parallelism": f"scene-shard x{world}",
-                   "migrations_per_rank_per_frame": args.migrate / args.migrate_every if migrating else 0},
-        "migrations": {"out": moved[0], "in": moved[1], "backend": args.backend,
-                       "exchange": "C++ SceneShard (RCCL side communicator for tickets, ncclSend/Recv rows)"
-                       if shard_impl == "cpp" else "noahgameframe_amd/shard.py (process group)"}
-        if migrating else None,
-        "roofline": {"bound": "hbm", "kernel": dom, "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                     "frac": achieved / HBM_PEAK_GBS, "traffic": traffic,
-                     "traffic_source": traffic_src, "traffic_rw": traffic_rw, "alg_bytes_rw": alg_rw,
-                     "mix_ceiling": ceiling},
-        "kernels": kern,
-        "per_frame": {"prop_events": s["n_prop_events"], "rec_events": s["n_rec_events"], "fired": s["n_fired"],
-                      "msgs": s["n_msgs"], "alg_bytes_all_kernels": total_alg,
-                      "frame_GBps_alg": total_alg / (elapsed / args.steps) / 1e9},
-        "cpu_baseline": None,
-    }
+    out["roofline"] = {"bound": "hbm", "kernel": dom, "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                       "frac": achieved / HBM_PEAK_GBS, "traffic": traffic,
+                       "traffic_source": traffic_src, "traffic_rw": traffic_rw, "alg_bytes_rw": alg_rw,
+                       "mix_ceiling": ceiling}
+    out["kernels"] = kern
+    out["per_frame"].update({"alg_bytes_all_kernels": total_alg,
+                             "frame_GBps_alg": total_alg / (elapsed / args.steps) / 1e9})
+    out["cpu_baseline"] = None
     # a launch-bound world: the per-kernel HIP events around every launch outlast the frame itself, so
     # that kernel time (and a bandwidth from it) is no evidence
     if d["avg_us"] * 1e-3 > out["ms_per_step"]:
@@ -567,15 +658,16 @@ def main():
         out["roofline"]["achieved"] = None
         out["roofline"]["note"] = (f"launch-bound: {dom}'s HIP-event time ({d['avg_us']:.1f} us) exceeds the frame "
                                    f"({out['ms_per_step'] * 1000:.1f} us); no bandwidth claimed")
-    # what the timed frame produces for the fan-out: the recipient runs per tile; each event's message
-    # offset is counted on the device when a consumer reads the frame (k_counted_moff), not in it
-    out["per_frame"]["message_offsets"] = ("produced at read time by k_counted_moff (nfk_outputs_get / nfk_read_*), "
-                                           "outside the timed frame; the headline loop's nfk_outputs_get builds "
-                                           "the dense ranks")
+
+
+def full_legs(args, out, rank, world, adapter, t_start, torch, kernel, workload):
+    """--full: the legs beside the headline (each with its own auto / off switch), added to the
+    result line."""
     def progress(what):  # (a line on stderr per leg: the run is visibly alive between legs)
         if rank == 0:
             print(f"bench.py: {what} ({time.perf_counter() - t_start:.0f} s)", file=sys.stderr, flush=True)
     progress("headline frames timed")
+    args = leg_args(args)
     if rank == 0 and world == 1 and args.config == 1 and args.host_calls == "auto":
         out["host_calls"] = host_calls_run(args, torch, kernel, workload)
         progress("host_calls leg done")
@@ -592,10 +684,6 @@ def main():
         progress("adapter_frame config[1] leg done")
         out["adapter_frame"]["config0"] = adapter_config0_run(args)
         progress("adapter_frame config[0] leg done")
-    if rank == 0:
-        print(json.dumps(out), flush=True)
-    if world > 1:
-        dist.destroy_process_group()
 
 
 def other_config_legs(args, progress=lambda what: None):
@@ -604,7 +692,7 @@ def other_config_legs(args, progress=lambda what: None):
     throughput, frame time, dominant kernel and roofline fraction."""
     legs = {}
     for c in (0, 3, 4):
-        cmd = [sys.executable, os.path.abspath(__file__), "--config", str(c), "--steps", str(args.steps),
+        cmd = [sys.executable, os.path.abspath(__file__), "--full", "--config", str(c), "--steps", str(args.steps),
                "--warmup", str(args.warmup), "--cpu-baseline", args.cpu_baseline, "--cpu-seconds", "8",
                "--other-configs", "off"]
         env = dict(os.environ)
@@ -636,11 +724,11 @@ def other_config_legs(args, progress=lambda what: None):
     return legs
 
 
-ADAPTER_EXE = os.path.join(ROOT, "tests", "cpp", "_ref", "adapter_bench")
+ADAPTER_EXE = os.path.join(ROOT, "oracle", "_ref", "adapter_bench")
 
 
 class AdapterLeg:
-    """The drop-in path at config[1]: tests/cpp/_ref/adapter_bench — a NoahGameFrame server with the
+    """The drop-in path at config[1]: oracle/_ref/adapter_bench — a NoahGameFrame server with the
     reference-side plugin (NFGPUKernelAdapter, NFGPUSceneAOIAdapter, NFGPUScheduleAdapter) in
     NFKernelPlugin's place among the reference's own modules — on the plugin_frame leg's world (1M
     entities, a heartbeat functor on every schedule, a common property / record callback, the AOI
@@ -654,7 +742,7 @@ class AdapterLeg:
     def __init__(self, args):
         self.procs, self.err = [], None
         if not os.path.exists(ADAPTER_EXE):
-            self.err = "tests/cpp/_ref/adapter_bench not built (needs /root/reference at build time)"
+            self.err = "oracle/_ref/adapter_bench not built (needs the reference tree at build time)"
             return
         from noahgameframe_amd import nfio, workload
         self.tmp = tempfile.TemporaryDirectory()
@@ -715,7 +803,7 @@ def adapter_config0_run(args):
     scanned on the device, the functor on the host), a per-object callback on every object's World
     property, and OnEvent's SetPropertyInt(self, "World", v) on 1 % of the objects per frame."""
     if not os.path.exists(ADAPTER_EXE):
-        return {"error": "tests/cpp/_ref/adapter_bench not built"}
+        return {"error": "oracle/_ref/adapter_bench not built"}
     from noahgameframe_amd import nfio, workload
     w = workload.tutorial3_world(n_ticks=args.warmup + args.steps, tick_ms=args.tick_ms)
     with tempfile.TemporaryDirectory() as d:
@@ -822,7 +910,7 @@ def host_calls_run(args, torch, kernel, workload):
     m.close()
     n_set = int(np.sum((w["x_tick"] >= args.warmup))) / args.steps
     n_sched = int(np.sum((w["h_tick"] >= args.warmup))) / args.steps
-    return {"value": args.entities * args.steps / elapsed, "unit": "entity-ticks/s",
+    return {"value": args.entities * args.steps / elapsed, "unit": "entity-ticks/s", "steps": args.steps,
             "ms_per_step": 1000.0 * elapsed / args.steps,
             "host_ms_per_frame": {"queue_calls": 1000.0 * t_calls / args.steps,
                                   "nfk_execute": 1000.0 * t_exec / args.steps},

@@ -2,7 +2,7 @@
 // plugin (integration/NFGPUKernelPlugin.cpp: NFGPUKernelAdapter, NFGPUSceneAOIAdapter,
 // NFGPUScheduleAdapter) in NFKernelPlugin's place, with the reference's own NFCKernelModule (under the
 // adapter), NFCSceneAOIModule (under the AOI adapter), NFCEventModule, NFCScheduleModule, NFCClassModule
-// and NFCElementModule compiled from /root/reference where they lie (tests/cpp/Makefile.adapter).  A
+// and NFCElementModule compiled from the reference tree where they lie (oracle/Makefile.adapter).  A
 // workload world (bench.py writes BASELINE config[1] or config[0]) is created through
 // NFIKernelModule::CreateObject with the class schema read from Struct XML, and the game logic a
 // server registers is in place:

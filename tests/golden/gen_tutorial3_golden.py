@@ -1,5 +1,5 @@
 """Writes tests/golden/tutorial3_10k.json: per-frame line counts and digests of the reference's own server
-(tests/cpp/_ref/tutorial3_session_ref: Tutorial3 unchanged on NFKernelPlugin's modules, compiled from
+(oracle/_ref/tutorial3_session_ref: Tutorial3 unchanged on NFKernelPlugin's modules, compiled from
 /root/reference) at 10k objects, for tests/test_tutorial3.py.  TEST INFRASTRUCTURE ONLY."""
 import json
 import os

@@ -1,7 +1,7 @@
 """The reference-side plugin (integration/NFGPUKernelPlugin.cpp) run as a NoahGameFrame server runs
 it: tests/cpp/adapter_session.cpp builds the reference's own NFCKernelModule (under the adapter),
 NFCSceneAOIModule, NFCEventModule, NFCClassModule and NFCElementModule from /root/reference
-(tests/cpp/Makefile.adapter), loads the workload's class schema from Struct XML, and replays the
+(oracle/Makefile.adapter), loads the workload's class schema from Struct XML, and replays the
 workload through NFIKernelModule / NFIScheduleModule.  The common property / record callbacks and
 the AOI module's recipient lists must match the oracle frame by frame."""
 import os
@@ -14,7 +14,7 @@ from noahgameframe_amd import nfio, workload
 from tests.parity import compare_runs, run_oracle
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-EXE = os.path.join(ROOT, "tests", "cpp", "_ref", "adapter_session")
+EXE = os.path.join(ROOT, "oracle", "_ref", "adapter_session")
 
 
 def _world(seed, **kw):

@@ -15,8 +15,8 @@ import subprocess
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-GPU_EXE = os.path.join(ROOT, "tests", "cpp", "_ref", "tutorial3_session")
-REF_EXE = os.path.join(ROOT, "tests", "cpp", "_ref", "tutorial3_session_ref")
+GPU_EXE = os.path.join(ROOT, "oracle", "_ref", "tutorial3_session")
+REF_EXE = os.path.join(ROOT, "oracle", "_ref", "tutorial3_session_ref")
 GOLDEN = os.path.join(ROOT, "tests", "golden", "tutorial3_10k.json")
 ARGS_10K = ("10000", "24", "500")  # objects, frames, tick ms
 

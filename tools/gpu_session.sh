@@ -27,10 +27,10 @@ for step in "$@"; do
     smoke) run smoke 300 python -c "import __graft_entry__ as g; g.smoke()" ;;
     tests) run tests 900 python -u -m pytest tests -m gpu -v --maxfail=5 -p no:cacheprovider \
              --timeout 300 --timeout-method thread ;;
-    bench) run bench 600 python bench.py --steps 50 --warmup 5 ;;
-    bench0) run bench0 600 python bench.py --config 0 --steps 50 --warmup 5 ;;
-    bench3) run bench3 600 python bench.py --config 3 --steps 20 --warmup 3 ${CPUB:---cpu-baseline off} ;;
-    bench4) run bench4 600 python bench.py --config 4 --steps 20 --warmup 3 ${CPUB:---cpu-baseline off} ;;
+    bench) run bench 600 python bench.py --full --steps 50 --warmup 5 ;;
+    bench0) run bench0 600 python bench.py --full --config 0 --steps 50 --warmup 5 ;;
+    bench3) run bench3 600 python bench.py --full --config 3 --steps 20 --warmup 3 ${CPUB:---cpu-baseline off} ;;
+    bench4) run bench4 600 python bench.py --full --config 4 --steps 20 --warmup 3 ${CPUB:---cpu-baseline off} ;;
     bench2g) NFGPU_BENCH_TRACE=1 run bench2g 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 \
                --master-port 29561 bench.py --gpus 2 --steps 20 --warmup 3 --backend gloo --cpu-baseline off \
                --entities 262144 --groups 1024 --migrate 128 ;;
@@ -57,7 +57,7 @@ for step in "$@"; do
     repeat) run repeat 900 tools/repeat_test.sh "$TAG/repeat" ${RR:-3} "${RK:-plugin_shard_replay}" ;;
     repeatpack) LIBDIR=ab/pack run repeatpack 900 tools/repeat_test.sh "$TAG/repeatpack" ${RR:-3} "${RK:-plugin_shard_replay}" ;;
     repeatbase) LIBDIR=ab/base run repeatbase 900 tools/repeat_test.sh "$TAG/repeatbase" ${RR:-3} "${RK:-plugin_shard_replay}" ;;
-    pluginbench) run pluginbench 600 python bench.py --steps 20 --warmup 3 --cpu-baseline off --host-calls off ;;
+    pluginbench) run pluginbench 600 python bench.py --full --steps 20 --warmup 3 --cpu-baseline off --host-calls off ;;
     membership) NFGPU_TRACE_MEMBERSHIP=1 run membership 300 python tools/membership_bench.py ;;
     selfmigcpp) run selfmigcpp 300 python bench.py --self-migrate --shard cpp --steps 24 --warmup 8 --cpu-baseline off \
                --host-calls off --plugin-frame off --other-configs off ;;
@@ -82,7 +82,7 @@ for step in "$@"; do
       run pmc_summary 60 python tools/pmc_summary.py --calib "$OUT/calib_fetch" "$OUT/calib_write" \
         --bench "$OUT/pmc_fetch" "$OUT/pmc_write" --sq "$OUT/pmc_sq" ${ALG:+--alg "$ALG"} \
         --out "$OUT/pmc_traffic.json" ;;
-    abifloor) run abifloor 120 tools/_bin/ref_abi_floor ;;
+    abifloor) run abifloor 120 oracle/_ref/ref_abi_floor ;;
     *) echo "unknown step $step" ;;
   esac
 done

@@ -1,4 +1,4 @@
-"""(debugging aid) run tests/cpp/_ref/logic_session (GPU plugin) and logic_session_ref on one seed / mode
+"""(debugging aid) run oracle/_ref/logic_session (GPU plugin) and logic_session_ref on one seed / mode
 and print the first frame where their fired lists, component logs or cross-object reads differ."""
 import os
 import subprocess

@@ -20,7 +20,7 @@ step() {  # step <name> <seconds> <cmd...>
 step calib_fetch 120 rocprofv3 --pmc FETCH_SIZE --output-format csv -d "$OUT/calib_fetch" -o run -- tools/_bin/pmc_calib
 step calib_write 120 rocprofv3 --pmc WRITE_SIZE --output-format csv -d "$OUT/calib_write" -o run -- tools/_bin/pmc_calib
 for c in "${@:-1 3 4}"; do
-  B="python bench.py --config $c --steps 20 --warmup 3 --cpu-baseline off --host-calls off --plugin-frame off --other-configs off --adapter-frame off"
+  B="python bench.py --full --config $c --steps 20 --warmup 3 --cpu-baseline off --host-calls off --plugin-frame off --other-configs off --adapter-frame off"
   step bench$c 300 $B
   step pmc_fetch$c 300 rocprofv3 --pmc FETCH_SIZE --output-format csv -d "$OUT/pmc_fetch$c" -o run -- $B
   step pmc_write$c 300 rocprofv3 --pmc WRITE_SIZE --output-format csv -d "$OUT/pmc_write$c" -o run -- $B

@@ -6,19 +6,19 @@ set -eu
 ROOT=$(pwd)
 TAG=${1:-c0}
 export TMPDIR=/tmp
-mkdir -p gpurun_out/$TAG
+OUT=$(realpath -m "${OUT:?set OUT to the directory the results go under}/$TAG"); mkdir -p "$OUT"
 python -c "
 import sys; sys.path.insert(0,'.')
 from noahgameframe_amd import nfio, workload
 nfio.write('/tmp/t3a.nfio', workload.tutorial3_world(n_ticks=60, tick_ms=100))
 nfio.write('/tmp/t3b.nfio', workload.tutorial3_world(n_ticks=20010, tick_ms=100))"
-timeout -k 10 120 tests/cpp/_ref/adapter_bench /tmp/t3a.nfio 10 50 1 > gpurun_out/$TAG/run.txt
+timeout -k 10 120 oracle/_ref/adapter_bench /tmp/t3a.nfio 10 50 1 > $OUT/run.txt
 echo "run rc=$?"
-NFGPU_TRACE_EXEC=1 timeout -k 10 120 tests/cpp/_ref/adapter_bench /tmp/t3a.nfio 10 50 1 > gpurun_out/$TAG/run_trace.txt 2> gpurun_out/$TAG/trace.txt
+NFGPU_TRACE_EXEC=1 timeout -k 10 120 oracle/_ref/adapter_bench /tmp/t3a.nfio 10 50 1 > $OUT/run_trace.txt 2> $OUT/trace.txt
 echo "trace rc=$?"
-timeout -k 10 300 rocprofv3 --kernel-trace --memory-copy-trace --stats --output-format csv -d $ROOT/gpurun_out/$TAG/prof -o c0 -- tests/cpp/_ref/adapter_bench /tmp/t3a.nfio 10 50 1 > gpurun_out/$TAG/run_prof.txt 2>&1
+timeout -k 10 300 rocprofv3 --kernel-trace --memory-copy-trace --stats --output-format csv -d $OUT/prof -o c0 -- oracle/_ref/adapter_bench /tmp/t3a.nfio 10 50 1 > $OUT/run_prof.txt 2>&1
 echo "rocprof rc=$?"
-cd gpurun_out/$TAG
+cd $OUT
 timeout -k 10 300 $ROOT/tools/_bin/adapter_bench_pg /tmp/t3b.nfio 10 20000 1 > run_pg.txt 2>&1
 echo "pg rc=$?"
 gprof -b $ROOT/tools/_bin/adapter_bench_pg gmon.out > gprof.txt
