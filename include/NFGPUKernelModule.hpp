@@ -32,6 +32,12 @@
 //   * Limits: 64 int + 64 float + 32 object frame properties (128 in all), 15 classes, 32 schedule names, 8 records of at
 //     most 64 rows x 16 columns, 4 ops per heartbeat program, 12 properties written by programs,
 //     16383 players per scene group (nfgpu.h).
+//   * A heartbeat program may guard a property op on an int property or on an int record cell
+//     (NFK_GUARD_CELL: `if (GetRecordInt(self, rec, row, col) <= 0) SetPropertyInt(...)`), compared
+//     with a 13-bit constant or an int property; guards on record ops, on f64 / object cells and
+//     comparisons of two cells have no device form (such a heartbeat keeps its host functor).  The
+//     cell's record must exist (AddRecord, or the class module's records) by AfterInit, where programs
+//     are resolved; on the C-ABI nfk_define_record of it comes before nfk_define_kind.
 //   * String / Vector properties stay host-side (not on the frame path); object (NFGUID) properties
 //     are device columns like the int / float ones.
 #pragma once
@@ -334,8 +340,9 @@ public:
     // module): a property operand (dst of a property op, a / lo / hi under NFK_A_PROP / NFK_LO_PROP /
     // NFK_HI_PROP, FLERP's a, the guard's property under NFK_GUARD and, with NFK_GUARD_PROP, the
     // property it is compared to in guard >> 19) is an index into props, a record
-    // op's dst is index << 8 | column with the index into records; resolved at AfterInit (a
-    // guard's constant, NFK_GUARD_K, is kept as it is)
+    // op's dst is index << 8 | column with the index into records, and so is the record field (bits
+    // 10..12) of an NFK_GUARD_CELL guard's cell, whose row and column are kept; resolved at AfterInit
+    // (a guard's constant, NFK_GUARD_K, is kept as it is)
     void AddHeartBeatProgram(const std::string& name, const std::vector<nfk_op>& ops,
                              const std::vector<std::string>& props, const std::vector<std::string>& records = {});
     int PropertyId(const std::string& name) const;

@@ -69,7 +69,21 @@ extern "C" {
  * to int property (guard >> 19) instead of 0 (both as the program has left them):
  * `if (GetPropertyInt(self, g) > GetPropertyInt(self, h)) ...`.  Without it, bits 19..31 hold a
  * signed constant K in [-4096, 4095] (NFK_GUARD_K; 0 by default) that g is compared to instead:
- * `if (GetPropertyInt(self, g) > 10) ...` (>= K and < K are > K-1 and <= K-1). */
+ * `if (GetPropertyInt(self, g) > 10) ...` (>= K and < K are > K-1 and <= K-1).
+ * NFK_GUARD_CELL (with NFK_GUARD, property ops only): bits 0..15 of guard name an int record cell
+ * instead of the property g, NFK_GUARD_CELL_ID(rec, row, col) = rec << 10 | row << 4 | col (13 bits;
+ * rec < NFK_MAX_RECORDS, row < NFK_MAX_REC_ROWS, col < NFK_MAX_REC_COLS); bits 16..31 keep their
+ * meaning (the comparison, then NFK_GUARD_PROP and the compared int property, or NFK_GUARD_K) — a
+ * functor's `if (GetRecordInt(self, "SkillTable", row, "CD") <= 0) SetPropertyInt(self, ...)`.  The
+ * guard reads NFCRecord::GetInt(row, col) (RC:616-635): the cell's value, or 0 when the record does
+ * not use the row, as the walk has left it so far — the cell after the window's queued SetRecordInt /
+ * AddRow / Remove / ClearRecord calls, then every RIADD_CLAMP on that (record, column) of a kind that
+ * fired for the entity earlier in schedule-name order or of an earlier op of the same program
+ * (wrapping add, clamp lo, clamp hi; applied only when the row is used, RC:182: an unused row reads
+ * 0 before and after).  The record ops themselves, their write-back and events stay with the record
+ * pass; they take no guard.  Guards on f64 cells and cell-to-cell comparisons are not expressible.
+ * The cell is checked against the record's shape at nfk_define_kind (the record must be defined
+ * first, as for a record op) and again at nfk_commit (a record may be redefined in between). */
 enum {
     NFK_OP_NOP = 0,
     NFK_OP_IADD_CLAMP = 1,
@@ -84,6 +98,8 @@ enum {
 #define NFK_LO_PROP 2
 #define NFK_HI_PROP 4
 #define NFK_GUARD 8
+#define NFK_GUARD_CELL 16 /* with NFK_GUARD: guard bits 0..15 name an int record cell (NFK_GUARD_CELL_ID) */
+#define NFK_GUARD_CELL_ID(rec, row, col) (((uint32_t)(rec) << 10) | ((uint32_t)(row) << 4) | (uint32_t)(col))
 #define NFK_GUARD_GT0 0 /* g > 0 */
 #define NFK_GUARD_LE0 1 /* g <= 0 */
 #define NFK_GUARD_NE0 2 /* g != 0 */
@@ -98,7 +114,8 @@ typedef struct nfk_op {
     uint8_t code;
     uint8_t flags;
     uint16_t dst;
-    uint32_t guard; /* with NFK_GUARD: property id | NFK_GUARD_* << 16 [| NFK_GUARD_PROP | h << 19 or | NFK_GUARD_K(k)]; else 0 */
+    uint32_t guard; /* with NFK_GUARD: property id (NFK_GUARD_CELL: NFK_GUARD_CELL_ID) | NFK_GUARD_* << 16
+                       [| NFK_GUARD_PROP | h << 19 or | NFK_GUARD_K(k)]; else 0 */
     int64_t a, b, c;
 } nfk_op; /* 32 bytes */
 
@@ -444,11 +461,20 @@ int nfk_rank_top(void* world, int32_t pid, int32_t k, int32_t* n_out, int64_t* g
 /* whether this world's frames run the specialised k_tick; msg: its kernel name or why not */
 int nfk_jit_status(void* world, int32_t* on, char* msg, int32_t cap);
 /* the specialisation for a schema without a world or a GPU: the generated policy source, and with
- * compile != 0 the hipRTC build for gfx950 (*ok = 1 on success, msg = the compiler log) */
+ * compile != 0 the hipRTC build for gfx950 (*ok = 1 on success, msg = the kernel's name, the compiler
+ * log, and after it the compiler's resource remarks of each kernel, one "name: value" per line after
+ * its "Function Name: ..." line — VGPRs, SGPRs Spill, VGPRs Spill, ScratchSize [bytes/lane], ...:
+ * the preview compiles with -Rpass-analysis=kernel-resource-usage, a world's commit does not) */
 int nfk_jit_preview(int32_t n_int, int32_t n_flt, int32_t n_class, int32_t n_kind,
                     const uint8_t* prop_flags /* [n_class][n_int + n_flt] */,
                     const nfk_op* ops /* [n_kind][NFK_MAX_OPS] */, const int32_t* n_ops /* [n_kind] */,
                     int32_t compile, int32_t* ok, char* src, int32_t src_cap, char* msg, int32_t msg_cap);
+/* the same for a schema whose programs guard on record cells (NFK_GUARD_CELL): the policy holds the
+ * records' shapes as literals (col_types [n_rec][NFK_MAX_REC_COLS], nullable: all int64) */
+int nfk_jit_preview_rec(int32_t n_int, int32_t n_flt, int32_t n_class, int32_t n_kind, const uint8_t* prop_flags,
+                        const nfk_op* ops, const int32_t* n_ops, int32_t n_rec, const int32_t* rec_rows /* [n_rec] */,
+                        const int32_t* rec_cols /* [n_rec] */, const uint8_t* col_types, int32_t compile, int32_t* ok,
+                        char* src, int32_t src_cap, char* msg, int32_t msg_cap);
 
 /* ---- measurement ---- */
 int nfk_set_profiling(void* world, int32_t on);

@@ -118,6 +118,26 @@ struct RecOp {
 // queued-SetProperty properties; slots [kMaxW, kMaxU) hold properties programs only read.
 constexpr int kMaxU = 16, kMaxW = 12;
 constexpr uint8_t kNoU = 0xFF;
+// A guard cell (NFK_GUARD_CELL) is one more read-only slot: its "property id" in the working-set
+// lists and Dev::u_pid is kCellPid | NFK_GUARD_CELL_ID, so the cells sort behind every property;
+// Dev::u_col of the slot is its record's cells, Dev::u_str the cells per entity (cols x rows).
+constexpr int kCellPid = 0x10000;
+constexpr uint32_t kNoCell = 0xFFFFFFFFu;
+__host__ __device__ __forceinline__ uint32_t cell_rec(uint32_t c) { return (c >> 10) & 7u; }
+__host__ __device__ __forceinline__ uint32_t cell_row(uint32_t c) { return (c >> 4) & 63u; }
+__host__ __device__ __forceinline__ uint32_t cell_col(uint32_t c) { return c & 15u; }
+static_assert(NFK_MAX_RECORDS == 8 && NFK_MAX_REC_ROWS == 64 && NFK_MAX_REC_COLS == 16, "NFK_GUARD_CELL_ID fields");
+// what a guard reads in a program op: the int property, or the pseudo-id of the record cell
+__host__ __device__ __forceinline__ int guard_id(const nfk_op& op) {
+    return (op.flags & NFK_GUARD_CELL) ? kCellPid | (int)(op.guard & 0x1FFFu) : (int)(op.guard & 0xFFFFu);
+}
+// k_records' RIADD_CLAMP on one cell (RC:182 SetInt of clamp(cell + a, lo, hi)): what a guard
+// cell's register takes when the walk passes such an op on its column
+__host__ __device__ __forceinline__ int64_t riadd_clamp(int64_t cur, int64_t a, int64_t lo, int64_t hi) {
+    int64_t r = (int64_t)((uint64_t)cur + (uint64_t)a);
+    r = r < lo ? lo : r;
+    return r > hi ? hi : r;
+}
 static_assert(kMaxW == NFK_MAX_TOUCH, "writable slots = touch capacity");
 
 // record op as k_records sees it (Dev::rops, kernel-argument space, so every field is a scalar):

@@ -978,7 +978,8 @@ bool build_u_tables(Tables& tab, int NK, std::vector<int>& wp, std::vector<int>&
                 } else if ((op.code == NFK_OP_ISET || op.code == NFK_OP_FSET) && (op.flags & NFK_A_PROP) && !is_w(op.a)) {
                     R.push_back((int)op.a);
                 }
-                if ((op.flags & NFK_GUARD) && !is_w(op.guard & 0xFFFF)) R.push_back((int)(op.guard & 0xFFFF));
+                // (a guard cell, NFK_GUARD_CELL: its pseudo-id, behind every property; never writable)
+                if ((op.flags & NFK_GUARD) && !is_w(guard_id(op))) R.push_back(guard_id(op));
                 if ((op.flags & NFK_GUARD) && (op.guard & NFK_GUARD_PROP) && !is_w(op.guard >> 19))
                     R.push_back((int)(op.guard >> 19));
             }
@@ -1015,7 +1016,7 @@ bool build_u_tables(Tables& tab, int NK, std::vector<int>& wp, std::vector<int>&
                     u[0] = slot(op.dst);
                     if (op.flags & NFK_A_PROP) u[1] = slot(op.a);
                 }
-                tab.opg[k][i] = (op.flags & NFK_GUARD) ? slot(op.guard & 0xFFFF) : kNoU;
+                tab.opg[k][i] = (op.flags & NFK_GUARD) ? slot(guard_id(op)) : kNoU;
                 tab.opg2[k][i] = ((op.flags & NFK_GUARD) && (op.guard & NFK_GUARD_PROP)) ? slot(op.guard >> 19) : kNoU;
                 for (int q = 0; q < 6; q++) {  // writable bits | read-only bits << 16
                     const uint8_t uq = q < 4 ? u[q] : q == 4 ? tab.opg[k][i] : tab.opg2[k][i];
@@ -1024,6 +1025,14 @@ bool build_u_tables(Tables& tab, int NK, std::vector<int>& wp, std::vector<int>&
                 OpX& x = tab.opx[k][i];
                 x.cfd = (uint32_t)op.code | ((uint32_t)op.flags << 8) | ((uint32_t)op.dst << 16);
                 x.slots = (uint32_t)u[0] | ((uint32_t)u[1] << 8) | ((uint32_t)u[2] << 16) | ((uint32_t)u[3] << 24);
+                if (op.code == NFK_OP_RIADD_CLAMP) {
+                    // a record op has no U slots: the word holds the read-only indices of the guard
+                    // cells on its column, which take the op in the walk (run_programs_u)
+                    x.slots = 0;
+                    for (size_t r = 0; r < R.size(); r++)
+                        if (R[r] >= kCellPid && (cell_rec((uint32_t)R[r]) << 8 | cell_col((uint32_t)R[r])) == op.dst)
+                            x.slots |= 1u << r;
+                }
                 x.a = op.a;
                 x.b = op.b;
                 x.c = op.c;
@@ -1050,6 +1059,12 @@ void fill_u_dev(Dev& d, const Tables& tab, const std::vector<int>& wp, const std
     for (int i = 0; i < kMaxW; i++) d.u_order[i] = i < n_w ? i : 0;  // (wp is in property-id order)
     for (int j = 0; j < kMaxU; j++) {
         const int p = d.u_pid[j];
+        if (p >= kCellPid) {  // a guard cell: its record's cells, cols x rows per entity
+            const uint32_t r = cell_rec((uint32_t)p);
+            d.u_col[j] = d.rcells[r];
+            d.u_str[j] = tab.rec_rows[r] * tab.rec_cols[r];
+            continue;
+        }
         d.u_col[j] = (p < 0 || !d.pmem) ? nullptr : d.pmem + tab.p_off[p];
         d.u_str[j] = p < 0 ? 0 : tab.p_str[p];
     }
@@ -1857,6 +1872,20 @@ int nfk_define_record(void* world, int32_t rec, int32_t rows, int32_t cols, cons
     return NFK_OK;
 }
 
+// an NFK_GUARD_CELL op's cell: a defined record, a row and column inside its shape, an int column
+static int check_guard_cell(World* w, const nfk_op& op) {
+    if (op.guard & 0xE000u) return fail(NFK_ERR_ARG, "NFK_GUARD_CELL: guard bits 13..15 must be 0 (NFK_GUARD_CELL_ID)");
+    const uint32_t c = op.guard & 0x1FFFu;
+    const int r = (int)cell_rec(c), row = (int)cell_row(c), col = (int)cell_col(c);
+    if (r >= w->cfg.n_rec || !w->rec_defined[r]) return fail(NFK_ERR_ARG, "NFK_GUARD_CELL: undefined record " + std::to_string(r));
+    if (row >= w->tab.rec_rows[r])
+        return fail(NFK_ERR_ARG, "NFK_GUARD_CELL: row " + std::to_string(row) + " outside record " + std::to_string(r) + "'s rows");
+    if (col >= w->tab.rec_cols[r])
+        return fail(NFK_ERR_ARG, "NFK_GUARD_CELL: column " + std::to_string(col) + " outside record " + std::to_string(r) + "'s columns");
+    if (w->rec_ctype[r][col] != 0) return fail(NFK_ERR_ARG, "NFK_GUARD_CELL: the guard's column is not an int column");
+    return NFK_OK;
+}
+
 int nfk_define_kind(void* world, int32_t kind, const nfk_op* ops, int32_t n_ops) {
     World* w = (World*)world;
     if (!w || kind < 0 || kind >= w->cfg.n_kind || n_ops < 0 || n_ops > NFK_MAX_OPS || (n_ops && !ops))
@@ -1871,9 +1900,16 @@ int nfk_define_kind(void* world, int32_t kind, const nfk_op* ops, int32_t n_ops)
             const bool rec = op.code == NFK_OP_RIADD_CLAMP || op.code == NFK_OP_RFAFFINE;
             // (NFK_GUARD_PROP: compared to the int property guard >> 19; otherwise to the constant
             // NFK_GUARD_KVAL(guard) in bits 19..31, any value)
-            const bool vs = (op.guard & NFK_GUARD_PROP) != 0;
-            if (rec || op.code == NFK_OP_NOP || !isint(op.guard & 0xFFFF) || (vs && !isint(op.guard >> 19)))
+            const bool vs = (op.guard & NFK_GUARD_PROP) != 0, cell = (op.flags & NFK_GUARD_CELL) != 0;
+            if (rec) return fail(NFK_ERR_ARG, "NFK_GUARD: a record op takes no guard");
+            if (op.code == NFK_OP_NOP || (!cell && !isint(op.guard & 0xFFFF)) || (vs && !isint(op.guard >> 19)))
                 return fail(NFK_ERR_ARG, "NFK_GUARD: a property op guarded by an int property");
+            if (cell) {
+                const int r = check_guard_cell(w, op);
+                if (r) return r;
+            }
+        } else if (op.flags & NFK_GUARD_CELL) {
+            return fail(NFK_ERR_ARG, "NFK_GUARD_CELL without NFK_GUARD");
         } else if (op.guard) {
             return fail(NFK_ERR_ARG, "nfk_op.guard without NFK_GUARD");
         }
@@ -1978,6 +2014,13 @@ int nfk_commit(void* world) {
     for (int r = 0; r < NR; r++)
         if (!w->rec_defined[r]) return fail(NFK_ERR_ARG, "record " + std::to_string(r) + " not defined");
 
+    // guard cells against the records' final shapes (a record may have been redefined after the kind)
+    for (int k = 0; k < NK; k++)
+        for (int i = 0; i < w->tab.nops[k]; i++)
+            if (w->tab.ops[k][i].flags & NFK_GUARD_CELL) {
+                const int r = check_guard_cell(w, w->tab.ops[k][i]);
+                if (r) return r;
+            }
     // record ops: compiled list sorted by (rec, col); distinct (rec, col) required
     int nro = 0;
     for (int k = 0; k < NK; k++)
@@ -2039,7 +2082,7 @@ int nfk_commit(void* world) {
                     add(op.dst, 1);
                     if (op.flags & NFK_A_PROP) add((int)op.a, 0);
                 }
-                if (op.flags & NFK_GUARD) add((int)(op.guard & 0xFFFF), 0);
+                if ((op.flags & NFK_GUARD) && !(op.flags & NFK_GUARD_CELL)) add((int)(op.guard & 0xFFFF), 0);
                 if ((op.flags & NFK_GUARD) && (op.guard & NFK_GUARD_PROP)) add((int)(op.guard >> 19), 0);
             }
         std::map<std::vector<int>, int> gi;
@@ -2081,7 +2124,7 @@ int nfk_commit(void* world) {
                     ps.push_back(op.dst);
                     if (op.flags & NFK_A_PROP) ps.push_back((int)op.a);
                 }
-                if (op.flags & NFK_GUARD) ps.push_back((int)(op.guard & 0xFFFF));
+                if ((op.flags & NFK_GUARD) && !(op.flags & NFK_GUARD_CELL)) ps.push_back((int)(op.guard & 0xFFFF));
                 if ((op.flags & NFK_GUARD) && (op.guard & NFK_GUARD_PROP)) ps.push_back((int)(op.guard >> 19));
             }
             for (size_t i = 1; i < ps.size(); i++) {
@@ -2167,7 +2210,6 @@ int nfk_commit(void* world) {
             off += 2 * (int64_t)cap + cpad;
         }
     }
-    set_working_set(w);
     ALLOC(d.s_hot, (size_t)std::max(NK, 1) * d.s_kstr * sizeof(SchedHot));
     ALLOC(d.s_cold, (size_t)std::max(NK, 1) * d.s_kstr * sizeof(SchedCold));
     ALLOC(d.e_flags, cap);
@@ -2180,6 +2222,7 @@ int nfk_commit(void* world) {
         ALLOC(d.rcells[r], (size_t)cap * w->tab.rec_rows[r] * w->tab.rec_cols[r] * 8);
         ALLOC(d.rused[r], (size_t)cap * 8);
     }
+    set_working_set(w);  // (after the records' arrays: a guard cell's slot points into them)
     ALLOC(w->pl_slot_w, (size_t)cap * 4);
     ALLOC(w->slot_obj_d, (size_t)cap * 4);
     ALLOC(w->fan_desc_w, (size_t)cap * 8);
@@ -3858,6 +3901,9 @@ static int execute_frame(World* w, int64_t now_ms, bool calls_only) {
         }
     }
     d.fuse_fan = d.msg_tcap != 0;
+    // a world whose programs guard on record cells (the cells are the last read-only slots): its
+    // library kernels are the DynSchemaCells instantiations
+    const bool cells = d.n_u > 0 && d.u_pid[d.n_u - 1] >= kCellPid;
     // A small world with no record pipeline after k_tick: its last tile ranks the frame's tiles
     // and the frame has no k_scan_tiles launch (profiles/r09a_*)
     d.lb_rank = (d.fuse_fan && !d.has_recops && d.n_tiles && d.n_tiles <= kLbMaxTiles &&
@@ -3899,16 +3945,21 @@ static int execute_frame(World* w, int64_t now_ms, bool calls_only) {
                 if (p < 128) m[p >> 6] |= 1ull << (p & 63);
             };
             uint64_t rd[NFK_MAX_KINDS][2] = {}, wr[NFK_MAX_KINDS][2] = {};
+            // ... and the record columns: a RIADD_CLAMP writes its (record, column), which the guard
+            // cells on that column read as the walk has left it (bit rec * 16 + col)
+            uint64_t rdc[NFK_MAX_KINDS][2] = {}, wrc[NFK_MAX_KINDS][2] = {};
             for (int k = 0; k < d.n_kind; k++)
                 for (int i = 0; i < w->tab.nops[k]; i++) {
                     const nfk_op& op = w->tab.ops[k][i];
+                    if (op.code == NFK_OP_RIADD_CLAMP) bit(wrc[k], (uint32_t)(op.dst >> 8) * 16u + (op.dst & 255u));
                     if (op.code != NFK_OP_IADD_CLAMP && op.code != NFK_OP_FLERP && op.code != NFK_OP_FAFFINE &&
                         op.code != NFK_OP_ISET && op.code != NFK_OP_FSET)
                         continue;
                     bit(wr[k], op.dst);
                     bit(rd[k], op.dst);
                     if (op.flags & NFK_GUARD) {
-                        bit(rd[k], op.guard & 0xFFFFu);
+                        if (op.flags & NFK_GUARD_CELL) bit(rdc[k], cell_rec(op.guard) * 16u + cell_col(op.guard));
+                        else bit(rd[k], op.guard & 0xFFFFu);
                         if (op.guard & NFK_GUARD_PROP) bit(rd[k], op.guard >> 19);
                     }
                     if (op.code == NFK_OP_FLERP || ((op.code == NFK_OP_ISET || op.code == NFK_OP_FSET) && (op.flags & NFK_A_PROP)))
@@ -3919,12 +3970,16 @@ static int execute_frame(World* w, int64_t now_ms, bool calls_only) {
                         if (op.flags & NFK_HI_PROP) bit(rd[k], (uint32_t)op.c);
                     }
                 }
-            uint64_t need[2] = {0, 0};  // what the re-run kinds after position k read
+            uint64_t need[2] = {0, 0}, needc[2] = {0, 0};  // what the re-run kinds after position k read
             for (int k = d.n_kind - 1; k >= 0; k--) {
-                if (!((kinds >> k) & 1) && ((wr[k][0] & need[0]) | (wr[k][1] & need[1]))) kinds |= 1u << k;
+                if (!((kinds >> k) & 1) &&
+                    ((wr[k][0] & need[0]) | (wr[k][1] & need[1]) | (wrc[k][0] & needc[0]) | (wrc[k][1] & needc[1])))
+                    kinds |= 1u << k;
                 if ((kinds >> k) & 1) {
                     need[0] |= rd[k][0];
                     need[1] |= rd[k][1];
+                    needc[0] |= rdc[k][0];
+                    needc[1] |= rdc[k][1];
                 }
             }
         }
@@ -3963,11 +4018,14 @@ static int execute_frame(World* w, int64_t now_ms, bool calls_only) {
                 void* args[] = {&d, &cd, &cc, (void*)&tcap, &kinds, &w0, &w1};
                 HIPCHK(hipModuleLaunchKernel(w->jit_chain_fn, (unsigned)nt, 1, 1, kTPB, 1, 1, 0, w->stream, args, nullptr));
             } else if (chain_u && use_u && d.n_u <= 8) {
-                hipLaunchKernelGGL((k_chain_u<8, DynSchema>), dim3((unsigned)nt), dim3(kTPB), 0, w->stream, d, cd, cc, tcap, kinds, w0, w1);
+                if (cells) hipLaunchKernelGGL((k_chain_u<8, DynSchemaCells>), dim3((unsigned)nt), dim3(kTPB), 0, w->stream, d, cd, cc, tcap, kinds, w0, w1);
+                else hipLaunchKernelGGL((k_chain_u<8, DynSchema>), dim3((unsigned)nt), dim3(kTPB), 0, w->stream, d, cd, cc, tcap, kinds, w0, w1);
             } else if (chain_u && use_u && d.n_u <= 12) {
-                hipLaunchKernelGGL((k_chain_u<12, DynSchema>), dim3((unsigned)nt), dim3(kTPB), 0, w->stream, d, cd, cc, tcap, kinds, w0, w1);
+                if (cells) hipLaunchKernelGGL((k_chain_u<12, DynSchemaCells>), dim3((unsigned)nt), dim3(kTPB), 0, w->stream, d, cd, cc, tcap, kinds, w0, w1);
+                else hipLaunchKernelGGL((k_chain_u<12, DynSchema>), dim3((unsigned)nt), dim3(kTPB), 0, w->stream, d, cd, cc, tcap, kinds, w0, w1);
             } else if (chain_u && use_u) {
-                hipLaunchKernelGGL((k_chain_u<16, DynSchema>), dim3((unsigned)nt), dim3(kTPB), 0, w->stream, d, cd, cc, tcap, kinds, w0, w1);
+                if (cells) hipLaunchKernelGGL((k_chain_u<16, DynSchemaCells>), dim3((unsigned)nt), dim3(kTPB), 0, w->stream, d, cd, cc, tcap, kinds, w0, w1);
+                else hipLaunchKernelGGL((k_chain_u<16, DynSchema>), dim3((unsigned)nt), dim3(kTPB), 0, w->stream, d, cd, cc, tcap, kinds, w0, w1);
             } else {
                 hipLaunchKernelGGL(k_chain, dim3((unsigned)nt), dim3(kTPB), 0, w->stream, d, w->chain_d, w->chain_cnt_d, tcap,
                                    kinds, w->chain_watch[0], w->chain_watch[1]);
@@ -3999,6 +4057,13 @@ static int execute_frame(World* w, int64_t now_ms, bool calls_only) {
             void* args[] = {&d};
             HIPCHK(hipModuleLaunchKernel(w->jit_fn, (unsigned)d.n_tiles, 1, 1, kTPB, 1, 1, (unsigned)lds, w->stream,
                                          args, nullptr));
+        } else if (use_u && cells) {  // the library's instantiations with the guard-cell loads and replay
+            if (d.n_u <= 8 && !(d.ablate & kAblWaves6))
+                hipLaunchKernelGGL((k_tick<kWavesU8, 8, DynSchemaCells>), g, b, lds, w->stream, d);
+            else if (d.n_u <= 12 && !(d.ablate & kAblWaves6))
+                hipLaunchKernelGGL((k_tick<kWavesU12, 12, DynSchemaCells>), g, b, lds, w->stream, d);
+            else
+                hipLaunchKernelGGL((k_tick<6, 16, DynSchemaCells>), g, b, lds, w->stream, d);
         } else if (use_u && d.n_u <= 8 && !(d.ablate & kAblWaves6))
             hipLaunchKernelGGL((k_tick<kWavesU8, 8>), g, b, lds, w->stream, d);
         else if (use_u && d.n_u <= 12 && !(d.ablate & kAblWaves6))
@@ -4831,6 +4896,15 @@ int nfk_jit_status(void* world, int32_t* on, char* msg, int32_t cap) {
 int nfk_jit_preview(int32_t n_int, int32_t n_flt, int32_t n_class, int32_t n_kind, const uint8_t* prop_flags,
                     const nfk_op* ops, const int32_t* n_ops, int32_t compile, int32_t* ok, char* src, int32_t src_cap,
                     char* msg, int32_t msg_cap) {
+    return nfk_jit_preview_rec(n_int, n_flt, n_class, n_kind, prop_flags, ops, n_ops, 0, nullptr, nullptr, nullptr, compile,
+                               ok, src, src_cap, msg, msg_cap);
+}
+
+int nfk_jit_preview_rec(int32_t n_int, int32_t n_flt, int32_t n_class, int32_t n_kind, const uint8_t* prop_flags,
+                        const nfk_op* ops, const int32_t* n_ops, int32_t n_rec, const int32_t* rec_rows,
+                        const int32_t* rec_cols, const uint8_t* col_types, int32_t compile, int32_t* ok, char* src,
+                        int32_t src_cap, char* msg, int32_t msg_cap) {
+    if (n_rec < 0 || n_rec > NFK_MAX_RECORDS || (n_rec && (!rec_rows || !rec_cols))) return fail(NFK_ERR_ARG, "bad records");
     if (!ok || !prop_flags || (n_kind && (!ops || !n_ops)) || n_int < 0 || n_flt < 0 || n_int > NFK_MAX_INT_PROPS ||
         n_flt > NFK_MAX_FLT_PROPS || n_class <= 0 || n_class >= NFK_MAX_CLASSES || n_kind < 0 || n_kind > NFK_MAX_KINDS)
         return fail(NFK_ERR_ARG, "bad schema");
@@ -4845,6 +4919,21 @@ int nfk_jit_preview(int32_t n_int, int32_t n_flt, int32_t n_class, int32_t n_kin
         tab->nops[k] = n_ops[k];
         for (int i = 0; i < n_ops[k]; i++) tab->ops[k][i] = ops[(size_t)k * NFK_MAX_OPS + i];
     }
+    for (int r = 0; r < n_rec; r++) {
+        if (rec_rows[r] <= 0 || rec_rows[r] > NFK_MAX_REC_ROWS || rec_cols[r] <= 0 || rec_cols[r] > NFK_MAX_REC_COLS)
+            return fail(NFK_ERR_ARG, "bad record shape");
+        tab->rec_rows[r] = rec_rows[r];
+        tab->rec_cols[r] = rec_cols[r];
+    }
+    for (int k = 0; k < n_kind; k++)  // the guard cells, as nfk_define_kind checks them
+        for (int i = 0; i < n_ops[k]; i++) {
+            const nfk_op& op = tab->ops[k][i];
+            if (!(op.flags & NFK_GUARD_CELL)) continue;
+            const uint32_t c = op.guard & 0x1FFFu, r = cell_rec(c);
+            if (!(op.flags & NFK_GUARD) || (op.guard & 0xE000u) || (int)r >= n_rec || (int)cell_row(c) >= rec_rows[r] ||
+                (int)cell_col(c) >= rec_cols[r] || (col_types && col_types[(size_t)r * NFK_MAX_REC_COLS + cell_col(c)] != 0))
+                return fail(NFK_ERR_ARG, "NFK_GUARD_CELL: not an int cell of a defined record");
+        }
     std::vector<int> wp, rp;
     const bool u_ok = build_u_tables(*tab, n_kind, wp, rp);
     Dev d{};
@@ -4864,8 +4953,28 @@ int nfk_jit_preview(int32_t n_int, int32_t n_flt, int32_t n_class, int32_t n_kin
         return NFK_OK;
     }
     const int u = std::max(d.n_u, 1), waves = kWavesJit;
-    JitBuild b = jit_compile(s, waves, u);
+    JitBuild b = jit_compile(s, waves, u, true);  // (with the kernels' resource usage in the log)
     *ok = b.ok;
+    if (b.ok) {
+        // the compiler's log as before (its warnings), then the kernels' resource remarks, each cut to
+        // "Function Name: ...", "VGPRs Spill: n", ... on a line of its own (a remark comes with its
+        // source line, a caret line and location notes: those are dropped)
+        std::istringstream in(b.log);
+        std::string line, other, usage_lines;
+        const std::string tag = " [-Rpass-analysis=kernel-resource-usage]";
+        bool in_remark = false;  // inside a remark's own lines, until the next warning or error begins
+        while (std::getline(in, line)) {
+            const size_t r = line.find("remark: "), t = line.find(tag);
+            if (r != std::string::npos && t != std::string::npos && t > r) {
+                usage_lines += line.substr(r + 8, t - r - 8) + "\n";
+                in_remark = true;
+                continue;
+            }
+            if (line.find("warning:") != std::string::npos || line.find("error:") != std::string::npos) in_remark = false;
+            if (!in_remark) other += line + "\n";
+        }
+        b.log = other + usage_lines;
+    }
     copy_msg(b.ok ? b.lowered + " (" + std::to_string(b.code.size()) + " B code object)\n" + b.log : b.log, msg, msg_cap);
     return NFK_OK;
 }

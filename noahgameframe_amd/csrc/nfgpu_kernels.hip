@@ -403,6 +403,7 @@ struct Ent {
     size_t cap;
     int n_int;
     int e;
+    uint32_t fired;  // the kinds that fire for the entity this frame (guard cells replay their record ops)
 
     __device__ __forceinline__ bool tget(uint32_t p, uint64_t& v) const {
         bool f = false;
@@ -459,6 +460,32 @@ struct Ent {
     }
 };
 
+// What an NFK_GUARD_CELL guard of op (k, i) reads: NFCRecord::GetInt(row, col) (RC:616-635) as the
+// walk has left it — 0 for a row the record does not use; else the cell (k_rsets / k_rrows have
+// applied the window's calls in place) with the RIADD_CLAMP ops on its column replayed that the
+// walk has passed: those of the kinds before k that fired, and of the ops before i in k's program
+// (k_records' arithmetic; the cell itself stays k_records').  row / col are inside the record's
+// shape (checked at commit), so the place is inside the entity's [cols][rows] cells.
+__device__ __forceinline__ int64_t guard_cell_value(Ent& en, const Tables* __restrict__ tab, uint32_t c, int k, int i) {
+    const Dev& d = *en.dv;
+    const uint32_t rec = cell_rec(c), row = cell_row(c), col = cell_col(c);
+    const int rows = tab->rec_rows[rec], cols = tab->rec_cols[rec];
+    const uint64_t used = d.rused[rec][en.e];
+    en.bytes += 8;
+    if (!((used >> row) & 1ull)) return 0;
+    int64_t v = (int64_t)d.rcells[rec][((size_t)en.e * cols + col) * rows + rec_pos(used, rec_rowm(rows), (int)row)];
+    en.bytes += 8;
+    for (int kk = 0; kk <= k; kk++) {
+        if (kk < k && !((en.fired >> kk) & 1u)) continue;
+        const int n = kk < k ? tab->nops[kk] : i;
+        for (int ii = 0; ii < n; ii++) {
+            const nfk_op& o = tab->ops[kk][ii];
+            if (o.code == NFK_OP_RIADD_CLAMP && o.dst == ((rec << 8) | col)) v = riadd_clamp(v, o.a, o.b, o.c);
+        }
+    }
+    return v;
+}
+
 // One heartbeat callback = the kind's program.  Pass 1 issues every operand load of the
 // program at once (independent loads, one memory round trip); pass 2 runs the ops in order,
 // reading a property from the frame's written-property list when an earlier op (or kind, or
@@ -486,8 +513,10 @@ __device__ __forceinline__ void run_program_chunk(Ent& en, const Tables* __restr
         pre[ii][0] = *prop_ptr(*en.dv, p0, en.e);
         en.bytes += 8;
         if (op.flags & NFK_GUARD) {
-            pre[ii][4] = *prop_ptr(*en.dv, op.guard & 0xFFFFu, en.e);
-            en.bytes += 8;
+            if (!(op.flags & NFK_GUARD_CELL)) {  // (a guard cell is read at its guard: guard_cell_value)
+                pre[ii][4] = *prop_ptr(*en.dv, op.guard & 0xFFFFu, en.e);
+                en.bytes += 8;
+            }
             if (op.guard & NFK_GUARD_PROP) {
                 pre[ii][5] = *prop_ptr(*en.dv, op.guard >> 19, en.e);
                 en.bytes += 8;
@@ -509,7 +538,9 @@ __device__ __forceinline__ void run_program_chunk(Ent& en, const Tables* __restr
         const nfk_op op = tab->ops[k][i];
         if (op.flags & NFK_GUARD) {
             uint64_t t;
-            const int64_t g = en.tget(op.guard & 0xFFFFu, t) ? (int64_t)t : (int64_t)pre[ii][4];
+            const int64_t g = (op.flags & NFK_GUARD_CELL) ? guard_cell_value(en, tab, op.guard & 0x1FFFu, k, i)
+                              : en.tget(op.guard & 0xFFFFu, t)  ? (int64_t)t
+                                                                : (int64_t)pre[ii][4];
             const int64_t h = !(op.guard & NFK_GUARD_PROP) ? (int64_t)NFK_GUARD_KVAL(op.guard) : en.tget(op.guard >> 19, t) ? (int64_t)t : (int64_t)pre[ii][5];
             if (!guard_ok((op.guard >> 16) & 3u, g, h)) continue;
         }
@@ -606,6 +637,7 @@ __global__ __launch_bounds__(kTPB) void k_tick_touch(Dev d) {
     en.cap = (size_t)d.cap;
     en.n_int = d.n_int;
     en.e = live ? e : 0;
+    en.fired = 0;
     en.bytes = dbytes;
     uint32_t fired = 0;
     uint32_t xh = 0;
@@ -627,6 +659,7 @@ __global__ __launch_bounds__(kTPB) void k_tick_touch(Dev d) {
         }
         // 2. NFCScheduleModule::Execute (SM:51-81)
         fired = sched_scan(d, e, en.bytes, desc);
+        en.fired = fired;
         // 3. the fired heartbeats' effect programs, in schedule-name order
         if (!(d.ablate & kAblPrograms) && fired) {
             for (int k = 0; k < d.n_kind; k++)
@@ -780,6 +813,7 @@ __global__ __launch_bounds__(kTPB) void k_chain(Dev d, ChainEnt* __restrict__ ou
         en.cap = (size_t)d.cap;
         en.n_int = d.n_int;
         en.e = e;
+        en.fired = fired;
         for (int k = 0; k < d.n_kind; k++)
             if ((fired >> k) & 1) run_program(en, d.tab, k, log);
     };

@@ -70,8 +70,11 @@ struct NoSetLog {
 };
 // The fired kinds' programs in schedule-name order on the register working set.  A Set that
 // fails the reference's change predicate leaves the value as it was; wm collects the slots a
-// Set changed at least once.
-template <int kU, class Log = NoSetLog>
+// Set changed at least once.  Bit 16 + j of wm, set by the caller: U slot j holds a guard cell whose
+// row the record uses (cell_loads); such a slot takes the RIADD_CLAMP ops the walk passes on its
+// column, so a later guard reads NFCRecord::GetInt as the walk has left it (an unused row reads 0
+// before and after, RC:616-635).  The cell itself, its write-back and events are k_records'.
+template <int kU, bool kCells = false, class Log = NoSetLog>
 __device__ __forceinline__ void run_programs_u(uint64_t (&v)[kU], uint32_t& wm, const Tables* __restrict__ tab_,
                                                uint32_t fired, int n_kind, uint32_t n_w, const Log& log = Log()) {
     CTables* tab = ctab(tab_);
@@ -130,6 +133,13 @@ __device__ __forceinline__ void run_programs_u(uint64_t (&v)[kU], uint32_t& wm, 
                 uput(v, u0, set ? rb : xb);
                 wm |= set ? (1u << u0) : 0u;
                 if (set) log(k, i, u0, xb, rb);
+            } else if (kCells && code == NFK_OP_RIADD_CLAMP) {
+                // (kCells: a world with guard cells, DynSchemaT<true>.  The op runs in k_records; sl: the read-only indices of the guard cells on its column)
+                for (uint32_t m = sl; m; m &= m - 1) {
+                    const uint32_t j = n_w + (uint32_t)__builtin_ctz(m);
+                    if ((wm >> (16 + j)) & 1)
+                        uput(v, j, (uint64_t)riadd_clamp((int64_t)uget(v, j), tab->opx[k][i].a, tab->opx[k][i].b, tab->opx[k][i].c));
+                }
             }
             // record ops run in k_records
         }
@@ -177,7 +187,11 @@ __device__ __forceinline__ T* elem(T* base, uint32_t i, uint32_t str = 1) {
 // order and fan-out classes.  DynSchema reads it at run time (Dev, kernel-argument scalars, and
 // Tables through the constant address space); a generated policy (nfgpu_host.hip, jit_source)
 // has the same members as constants and the programs as straight-line code on the registers.
-struct DynSchema {
+// kCells: the instantiations for a world whose programs guard on record cells (NFK_GUARD_CELL); a
+// world without such a guard launches DynSchemaT<false>, which has none of that code (its loops
+// and register allocation are what they were before the flag existed).
+template <bool kCells>
+struct DynSchemaT {
     static constexpr bool kStatic = false;
     static constexpr bool kOff32 = false;  // 64-bit element addresses (any world size)
     static constexpr uint32_t kSpecMask = 0;  // operands loaded before the fire test (none)
@@ -187,6 +201,12 @@ struct DynSchema {
     // kLbMaxTiles tiles compiles that code out (kLb = false) and the frame ranks by k_scan_tiles
     static constexpr bool kLb = true;
     static constexpr int kNK = NFK_MAX_KINDS;  // (an upper bound only)
+    // guard cells (NFK_GUARD_CELL): any U slot may hold one, told by its Dev::u_pid at run time
+    static constexpr uint32_t kCellMask = kCells ? 0xFFFFu : 0u;
+    __device__ static uint32_t u_cell(const Dev& d, int j) {
+        return d.u_pid[j] >= kCellPid ? (uint32_t)d.u_pid[j] & 0x1FFFu : kNoCell;
+    }
+    __device__ static int rec_rows(const Dev& d, uint32_t rec) { return ctab(d.tab)->rec_rows[rec]; }
     __device__ static int n_kind(const Dev& d) { return d.n_kind; }
     __device__ static int n_w(const Dev& d) { return d.n_w; }
     __device__ static uint32_t u_lower(const Dev& d, int j) { return d.u_lower[j]; }
@@ -213,9 +233,61 @@ struct DynSchema {
     }
     template <int kU, class Log = NoSetLog>
     __device__ static void run(uint64_t (&v)[kU], uint32_t& wm, const Dev& d, uint32_t fired, const Log& log = Log()) {
-        run_programs_u(v, wm, d.tab, fired, d.n_kind, d.n_w, log);
+        run_programs_u<kU, kCells>(v, wm, d.tab, fired, d.n_kind, d.n_w, log);
     }
 };
+
+// ---- guard cells (NFK_GUARD_CELL) ----
+// A policy names the U slots that may hold a record cell in kCellMask, with u_cell(d, j) = the
+// slot's NFK_GUARD_CELL_ID (kNoCell: a property) and rec_rows(d, rec).  A generated policy of a
+// world without cell guards has no such members and none of this code is instantiated for it.
+template <class S>
+constexpr auto cell_slots(int) -> decltype(S::kCellMask) {
+    return S::kCellMask;
+}
+template <class S>
+constexpr uint32_t cell_slots(long) {
+    return 0u;
+}
+template <class S>
+__device__ __forceinline__ bool slot_is_cell(const Dev& d, int j) {
+    if constexpr (cell_slots<S>(0) != 0)
+        return ((cell_slots<S>(0) >> j) & 1u) && S::u_cell(d, j) != kNoCell;
+    else
+        return false;
+}
+// The guard cells among the needed slots of entity e (e < N, a live slot): the record's used-row
+// mask, then — when the record uses the row — the cell at rec_pos(used, rowm, row) of the slot's
+// (entity, column) vector; an unused row leaves the register 0 and loads no cell.  row < rows and
+// col < cols (checked at commit), so the place is inside the entity's [cols][rows] cells.  Returns
+// the slots whose row is used.
+template <int kU, class S>
+__device__ __forceinline__ uint32_t cell_loads(const Dev& d, int e, uint32_t need, uint64_t (&v)[kU], unsigned& bytes) {
+    uint32_t cu = 0;
+    constexpr uint32_t km = cell_slots<S>(0);
+    if constexpr (km != 0) {
+#pragma unroll
+        for (int j = 0; j < kU; j++) {
+            if (!((km >> j) & 1u)) continue;
+            const uint32_t c = S::u_cell(d, j);
+            if (c == kNoCell || !((need >> j) & 1u)) continue;
+            const uint32_t rec = cell_rec(c), row = cell_row(c);
+            const int rows = S::rec_rows(d, rec);
+            const uint64_t used = *elem<S>(d.rused[rec], (uint32_t)e);
+            bytes += 8;
+            if ((used >> row) & 1ull) {
+                const uint32_t at = cell_col(c) * (uint32_t)rows + rec_pos(used, rec_rowm(rows), (int)row);
+                v[j] = *(elem<S>(d.u_col[j], (uint32_t)e, S::u_str(d, j)) + at);
+                cu |= 1u << j;
+                bytes += 8;
+            }
+        }
+    }
+    return cu;
+}
+
+typedef DynSchemaT<false> DynSchema;
+typedef DynSchemaT<true> DynSchemaCells;
 
 constexpr int kKindChunk = 8;  // schedule hot records loaded together per chunk
 // non-temporal hint bits of a schema policy's kNt (NFGPU_JIT_NT for the hipRTC specialisation)
@@ -441,7 +513,8 @@ __device__ __forceinline__ void tick_tile(const Dev& d, const int tile, unsigned
             if (!(d.ablate & kAblNoLoads))
 #pragma unroll
                 for (int j = 0; j < kU; j++)
-                    if ((S::kSpecMask >> j) & 1) v[j] = *elem<S>(d.u_col[j], (uint32_t)ec, S::u_str(d, j));
+                    if (((S::kSpecMask >> j) & 1) && !slot_is_cell<S>(d, j))
+                        v[j] = *elem<S>(d.u_col[j], (uint32_t)ec, S::u_str(d, j));
         }
         fired = sched_scan<S>(d, ec, bytes, desc, s_rem, e >= d.N);  // NFCScheduleModule::Execute (SM:51-81)
         desc = e < d.N ? desc : kDeadDesc;
@@ -460,17 +533,18 @@ __device__ __forceinline__ void tick_tile(const Dev& d, const int tile, unsigned
                 bytes += 8;
             }
     }
-    uint32_t need = 0;
+    uint32_t need = 0, cu = 0;  // cu: the guard-cell slots whose row is used
     if (live) {
         need = xset;
         if (!(d.ablate & kAblPrograms)) need |= S::need(d, fired);
         // one batch of independent loads: every value this entity's frame reads or writes
 #pragma unroll
         for (int j = 0; j < kU; j++)
-            if (((need >> j) & 1) && !((S::kSpecMask >> j) & 1) && !(d.ablate & kAblNoLoads)) {
+            if (((need >> j) & 1) && !((S::kSpecMask >> j) & 1) && !slot_is_cell<S>(d, j) && !(d.ablate & kAblNoLoads)) {
                 v[j] = ld_nt<(S::kNt & kNtColLoad) != 0>(elem<S>(d.u_col[j], (uint32_t)e, S::u_str(d, j)));
                 bytes += 8;
             }
+        if (!(d.ablate & kAblNoLoads)) cu = cell_loads<kU, S>(d, e, need, v, bytes);
     }
     if (live) {
 #pragma unroll
@@ -486,6 +560,7 @@ __device__ __forceinline__ void tick_tile(const Dev& d, const int tile, unsigned
             wm = xset;
         }
         // the fired heartbeats' effect programs, in schedule-name order
+        wm |= cu << 16;  // (run_programs_u: the used guard cells take the walk's record ops)
         if (!(d.ablate & (kAblPrograms | kAblNoRun)) && fired) S::run(v, wm, d, fired);
     }
     // dirty diff against the frame-start values
@@ -924,11 +999,14 @@ __global__ __launch_bounds__(kTPB) void k_chain_u(Dev d, ChainEnt* __restrict__ 
         fired = sched_scan<S, false>(d, e, bytes, desc) & kinds;
         if (desc_dead(desc)) fired = 0;
     }
+    uint32_t cu = 0;  // the guard-cell slots whose row is used (cell_loads)
     if (fired) {
         const uint32_t need = S::need(d, fired);
 #pragma unroll
         for (int j = 0; j < kU; j++)
-            if ((need >> j) & 1) v[j] = *elem<S>(d.u_col[j], (uint32_t)e, S::u_str(d, j));
+            if (((need >> j) & 1) && !slot_is_cell<S>(d, j)) v[j] = *elem<S>(d.u_col[j], (uint32_t)e, S::u_str(d, j));
+        unsigned bytes = 0;
+        cu = cell_loads<kU, S>(d, e, need, v, bytes);
     }
     const auto watched = [&](uint32_t u) {
         const uint32_t p = (uint32_t)S::u_pid(d, (int)u);
@@ -939,14 +1017,14 @@ __global__ __launch_bounds__(kTPB) void k_chain_u(Dev d, ChainEnt* __restrict__ 
         uint64_t c[kU];
 #pragma unroll
         for (int j = 0; j < kU; j++) c[j] = v[j];
-        uint32_t wm = 0;
+        uint32_t wm = cu << 16;
         S::run(c, wm, d, fired, [&](int, int, uint32_t u, uint64_t, uint64_t) { cnt += watched(u) ? 1u : 0u; });
     }
     unsigned long long tot;
     uint32_t at = (uint32_t)block_excl_scan(cnt, s_w, tot);
     if (cnt) {
         ChainEnt* t_out = out + (size_t)blockIdx.x * tcap;
-        uint32_t wm = 0;
+        uint32_t wm = cu << 16;
         S::run(v, wm, d, fired, [&](int k, int i, uint32_t u, uint64_t o, uint64_t n) {
             if (watched(u) && at < tcap)
                 t_out[at++] = ChainEnt{(uint32_t)e, (uint16_t)S::u_pid(d, (int)u), (uint8_t)k, (uint8_t)i, o, n};

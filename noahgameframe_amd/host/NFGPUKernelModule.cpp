@@ -93,7 +93,14 @@ static void resolve_program(std::vector<nfk_op>& ops, const std::vector<std::str
             return (int64_t)pid(props[(size_t)i]);
         };
         if (op.flags & NFK_GUARD) {
-            op.guard = (op.guard & ~0xFFFFu) | (uint32_t)P(op.guard & 0xFFFF);
+            if (op.flags & NFK_GUARD_CELL) {  // a record cell: its record (bits 10..12) is an index into records
+                const size_t r = (op.guard >> 10) & 63u;
+                if (r >= records.size()) throw std::runtime_error("heartbeat program: guard cell's record out of range");
+                const int id = rid(records[r]);
+                if (id < 0 || id >= NFK_MAX_RECORDS) throw std::runtime_error("heartbeat program: guard cell's record has no device id");
+                op.guard = (op.guard & ~0xFC00u) | ((uint32_t)id << 10);
+            } else
+                op.guard = (op.guard & ~0xFFFFu) | (uint32_t)P(op.guard & 0xFFFF);
             if (op.guard & NFK_GUARD_PROP)  // (the compared property, guard >> 19)
                 op.guard = (op.guard & 0x7FFFFu) | ((uint32_t)P(op.guard >> 19) << 19);
         }

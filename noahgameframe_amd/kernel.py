@@ -98,6 +98,8 @@ def load_library(path=LIB_PATH):
         "nfk_rank_top": [VP, I32, I32, VP, VP, VP, VP],
         "nfk_jit_status": [VP, VP, VP, I32], "nfk_membership_stats": [VP, VP, VP, VP, VP],
         "nfk_jit_preview": [I32, I32, I32, I32, VP, VP, VP, I32, VP, VP, I32, VP, I32],
+        "nfk_jit_preview_rec": [I32, I32, I32, I32, VP, VP, VP, I32, VP, VP, VP, I32, VP, VP, I32, VP, I32],
+        "nfk_watch_props": [VP, I32, VP], "nfk_read_chain": [VP, I32, VP, VP, VP, VP, VP, VP, VP],
         "nfk_load_object": [VP, I32, VP, VP], "nfk_set_objects": [VP, I32, VP, VP, VP, VP, VP],
         "nfk_get_objects": [VP, I32, VP, VP, VP, VP, VP], "nfk_read_object": [VP, I32, VP, VP],
         "nfk_read_events_obj": [VP, VP, VP], "nfk_record_rows": [VP, I32, VP, VP, VP, VP, VP, VP],
@@ -492,6 +494,24 @@ class NFKernelModule:
             out["ev_oldh"], out["ev_newh"] = oh
         return out
 
+    # ---- per-Set chains (NFIKernelModule::AddPropertyCallBack) ----
+    def watch_props(self, pids):
+        """nfk_watch_props: the int / f64 properties whose accepted program Sets every Execute logs
+        (an empty list watches nothing)"""
+        p = np.ascontiguousarray(pids, np.int32)
+        self._chk(self.lib.nfk_watch_props(self.h, len(p), _p(p)))
+
+    def read_chain(self):
+        """nfk_read_chain: the last Execute's per-Set log in the walk's order (NFGUID, kind, op) as a
+        dict of arrays obj, kind, op, pid, old, new"""
+        n = ctypes.c_int32()
+        self._chk(self.lib.nfk_read_chain(self.h, 0, ctypes.byref(n), None, None, None, None, None, None))
+        cap = n.value
+        a = [np.zeros(cap, np.int32) for _ in range(4)] + [np.zeros(cap, np.uint64) for _ in range(2)]
+        if cap:
+            self._chk(self.lib.nfk_read_chain(self.h, cap, ctypes.byref(n), *[_p(x) for x in a]))
+        return dict(zip(("obj", "kind", "op", "pid", "old", "new"), a))
+
     # ---- measurement ----
     def set_profiling(self, on):
         self._chk(self.lib.nfk_set_profiling(self.h, 1 if on else 0))
@@ -523,8 +543,17 @@ def jit_preview(w, compile=False):
     ok = ctypes.c_int32()
     src = ctypes.create_string_buffer(1 << 20)
     msg = ctypes.create_string_buffer(1 << 16)
-    rc = lib.nfk_jit_preview(n_int, n_flt, n_cls, n_kind, _p(flags), _p(ops), _p(n_ops), int(compile),
-                             ctypes.byref(ok), src, len(src), msg, len(msg))
+    n_rec = int(w["cfg"][5])
+    if n_rec:  # the records' shapes: a policy with guard cells (NFK_GUARD_CELL) holds them as literals
+        rows = np.ascontiguousarray(w["rec_rows"][:n_rec], np.int32)
+        cols = np.ascontiguousarray(w["rec_cols"][:n_rec], np.int32)
+        ct = np.zeros((n_rec, wl.MAX_REC_COLS), np.uint8)
+        ct[:, :] = np.asarray(w["rec_ctype"], np.uint8).reshape(n_rec, -1)[:, :wl.MAX_REC_COLS]
+        rc = lib.nfk_jit_preview_rec(n_int, n_flt, n_cls, n_kind, _p(flags), _p(ops), _p(n_ops), n_rec, _p(rows),
+                                     _p(cols), _p(ct), int(compile), ctypes.byref(ok), src, len(src), msg, len(msg))
+    else:
+        rc = lib.nfk_jit_preview(n_int, n_flt, n_cls, n_kind, _p(flags), _p(ops), _p(n_ops), int(compile),
+                                 ctypes.byref(ok), src, len(src), msg, len(msg))
     if rc != NFK_OK:
         raise NFKError(rc, lib.nfk_last_error().decode())
     return src.value.decode(), bool(ok.value), msg.value.decode()

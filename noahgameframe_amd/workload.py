@@ -40,6 +40,7 @@ KID = {n: i for i, n in enumerate(KINDS)}
 # op codes / flags (include/nfgpu.h)
 OP_IADD_CLAMP, OP_FLERP, OP_FAFFINE, OP_RIADD_CLAMP, OP_RFAFFINE, OP_ISET, OP_FSET = 1, 2, 3, 4, 5, 6, 7
 A_PROP, LO_PROP, HI_PROP, GUARD = 1, 2, 4, 8
+GUARD_CELL = 16
 GUARD_GT0, GUARD_LE0, GUARD_NE0, GUARD_EQ0 = 0, 1, 2, 3
 GUARD_PROP = 1 << 18
 GUARD_KMIN, GUARD_KMAX = -4096, 4095
@@ -51,6 +52,14 @@ def guard(pid, cmp, vs=None, k=0):
     `vs` (NFK_GUARD_PROP: a functor's `if (GetPropertyInt(self, g) > GetPropertyInt(self, h))`)"""
     assert GUARD_KMIN <= k <= GUARD_KMAX and (vs is None or k == 0)
     return pid | (cmp << 16) | ((k & 0x1FFF) << 19 if vs is None else GUARD_PROP | (vs << 19))
+
+
+def guard_cell(rec, row, col, cmp, vs=None, k=0):
+    """nfk_op.guard of an NFK_GUARD | NFK_GUARD_CELL op: the int record cell (NFK_GUARD_CELL_ID: rec << 10 |
+    row << 4 | col) and its comparison with the constant k or the int property `vs`, as guard() — a
+    functor's `if (GetRecordInt(self, rec, row, col) <= 0)`"""
+    assert 0 <= rec < 8 and 0 <= row < 64 and 0 <= col < 16
+    return guard((rec << 10) | (row << 4) | col, cmp, vs, k)
 
 
 MAX_OPS = 8  # include/nfgpu.h NFK_MAX_OPS (workload files written before round 4 hold 4 per kind)
@@ -178,7 +187,13 @@ def make_world(n_obj=4096, n_scenes=1, groups_per_scene=16, players_per_group=4,
                switch_frac=0.0, switch_new_groups=False, rec_steady=False, ext_props=None, burst_frac=0.0,
                burst_props=20, rmw_frac=0.0, spawn_frac=0.0, destroy_frac=0.0, rec_set_frac=0.0,
                rec_set_float=True, obj_props=False, obj_set_frac=0.05, rec_row_frac=0.0, set_ops=False,
-               lethal_poison=False, const_guards=False):
+               lethal_poison=False, const_guards=False, cell_guards=None):
+    """cell_guards=(case, twin[, overrides]): one of the twin worlds of CELL_GUARD_CASES[case] (its world
+    options, with the overrides — say a larger n_obj for a timing — replace the ones given here but
+    n_ticks and seed): twin "A" guards on mirror int properties, twin "B" on the record cells the
+    mirrors track (NFK_GUARD_CELL); see _cell_guard_world."""
+    if cell_guards is not None:
+        return _cell_guard_world(cell_guards[0], cell_guards[1], n_ticks, seed, *cell_guards[2:])
     if spawn_frac > 0 or destroy_frac > 0:
         return _lifecycle_world(locals())
     rng = np.random.default_rng(seed)
@@ -669,6 +684,218 @@ def _lifecycle_world(kw):
         w["rec0_used"][born >= 0] = 0
     w["born"] = born
     w["d_tick"], w["d_obj"] = d_tick, d_obj
+    return w
+
+
+# ---- twin worlds for guards on record cells (NFK_GUARD_CELL) ---------------------------------
+# Twin A guards on MIRROR int properties, twin B — the same workload byte for byte but for the guard
+# words — on the record cells the mirrors track.  Each mirror equals its cell's NFCRecord::GetInt value
+# (the cell, or 0 where the record does not use the row, RC:616-635) at every point a guard can read it:
+# it starts equal; a RIADD_CLAMP on the guard's column sits next to an IADD_CLAMP of the same delta and
+# bounds on each mirror of that column, in the same program; every window whose record calls change a
+# guard cell's GetInt value carries a SetPropertyInt of the mirror to the value the calls leave
+# (SetRecordInt -> its value, Remove / ClearRecord -> 0, AddRow -> the row's value); the random
+# SetProperty calls skip the mirrors.  Where an op would move 0 (a clamp with lo > 0) the mirror has no
+# op and the cells hold the op's fixed point, with no row calls.  Both twins carry the mirrored ops and
+# calls, so their outputs are identical in full.
+def _cg_programs(case):
+    """(guard cells [(rec, row, col)], mirrors [property], programs {kind: [op]}) of a case; an op's
+    guard is 0 or ("G", cell index, comparison, {k= | vs=})"""
+    P = PID
+    g = lambda c, cmp, **kw: ("G", c, cmp, kw)
+    hp_up = (OP_IADD_CLAMP, 0, P["HP"], 0, 5, 0, 5000)
+    hp_dn = (OP_IADD_CLAMP, 0, P["HP"], 0, -13, 1, 5000)
+    lerp = (OP_FLERP, 0, P["X"], 0, P["TargetX"], f64bits(0.125), 0)
+    cd = (OP_RIADD_CLAMP, 0, (0 << 8) | 1, 0, -100, 0, I64_MAX)
+    charge = (OP_RFAFFINE, 0, (0 << 8) | 2, 0, f64bits(0.5), f64bits(0.0), 0)
+    mcd = lambda m: (OP_IADD_CLAMP, 0, P[m], 0, -100, 0, I64_MAX)   # the mirror's twin of `cd`
+    if case in ("static", "calls"):
+        rows = 20 if case == "static" else 32
+        cells = [(0, 0, 1), (0, rows // 2 - 1, 1), (0, rows - 1, 1)]
+        mirrors = ["MAXSP", "SPREGEN", "NPCType"]
+        progs = {
+            "HPRegen": [hp_up,
+                        (OP_IADD_CLAMP, GUARD, P["Gold"], g(0, GUARD_GT0, k=30), 1, 0, 1 << 40),
+                        (OP_ISET, GUARD, P["EXP"], g(1, GUARD_LE0, k=-100), 5, 0, 0)],
+            "MPRegen": [(OP_ISET, GUARD, P["EXP"], g(2, GUARD_NE0), 7, 0, 0),
+                        (OP_IADD_CLAMP, GUARD, P["Gold"], g(0, GUARD_EQ0), 3, 0, 1 << 40)],
+            "Move": [lerp, (OP_FSET, A_PROP | GUARD, P["Z"], g(1, GUARD_GT0, k=30), P["TargetX"], 0, 0)],
+            "Patrol": [(OP_IADD_CLAMP, GUARD, P["Gold"], g(2, GUARD_GT0, vs=P["Level"]), -2, 0, 1 << 40)],
+            "Poison": [hp_dn,
+                       (OP_ISET, GUARD, P["EXP"], g(0, GUARD_GT0, k=GUARD_KMIN), 9, 0, 0),
+                       (OP_IADD_CLAMP, GUARD, P["EXP"], g(1, GUARD_LE0, k=GUARD_KMAX), 3, 0, 1 << 40),
+                       (OP_ISET, GUARD, P["Gold"], g(2, GUARD_LE0, k=-100), 1, 0, 0),
+                       (OP_IADD_CLAMP, GUARD, P["Gold"], g(2, GUARD_EQ0, k=30), 11, 0, 1 << 40)],
+            "SkillCD": [cd, charge] + [mcd(m) for m in mirrors]}
+    elif case == "replay":
+        # the record op in Move (every object, every frame): before a guarded op of its own program and
+        # before the guarded kinds Patrol and Poison; HPRegen, before both, sees the frame-start cell
+        cells, mirrors = [(0, 63, 1)], ["MAXSP"]
+        progs = {
+            "HPRegen": [hp_up, (OP_IADD_CLAMP, GUARD, P["Gold"], g(0, GUARD_LE0, k=1500), 1, 0, 1 << 40)],
+            "MPRegen": [(OP_IADD_CLAMP, 0, P["MP"], 0, 1, 0, 1000)],
+            "Move": [lerp, cd, mcd("MAXSP"),
+                     (OP_ISET, GUARD, P["EXP"], g(0, GUARD_LE0, k=1500), 1, 0, 0),
+                     (OP_ISET, GUARD, P["EXP"], g(0, GUARD_GT0, k=1500), 2, 0, 0)],
+            "Patrol": [(OP_IADD_CLAMP, GUARD, P["Gold"], g(0, GUARD_NE0), 7, 0, 1 << 40)],
+            "Poison": [hp_dn, (OP_IADD_CLAMP, GUARD, P["EXP"], g(0, GUARD_GT0, k=700), 3, 0, 1 << 40)],
+            "SkillCD": [charge]}
+    elif case == "unused_row_fixed_point":
+        # RIADD_CLAMP +1 [1000, 1999] on cells that all hold 1999: the op changes nothing, and would
+        # lift an unused row's 0 to 1000 if the replay touched it; the mirror has no op
+        cells, mirrors = [(0, 5, 0)], ["MAXSP"]
+        progs = {
+            "HPRegen": [hp_up, (OP_IADD_CLAMP, GUARD, P["Gold"], g(0, GUARD_EQ0), 1, 0, 1 << 40)],
+            "MPRegen": [(OP_IADD_CLAMP, 0, P["MP"], 0, 1, 0, 1000)],
+            "Move": [lerp, (OP_RIADD_CLAMP, 0, (0 << 8) | 0, 0, 1, 1000, 1999),
+                     (OP_IADD_CLAMP, GUARD, P["Gold"], g(0, GUARD_EQ0), 1, 0, 1 << 40),
+                     (OP_IADD_CLAMP, GUARD, P["EXP"], g(0, GUARD_GT0), 1, 0, 1 << 40)],
+            "Patrol": [(OP_ISET, GUARD, P["EXP"], g(0, GUARD_EQ0), 0, 0, 0)],
+            "Poison": [hp_dn, (OP_IADD_CLAMP, GUARD, P["Gold"], g(0, GUARD_GT0), -3, 0, 1 << 40)],
+            "SkillCD": [cd, charge]}
+    else:
+        raise ValueError(f"unknown cell-guard case {case!r}")
+    return cells, mirrors, progs
+
+
+CELL_GUARD_CASES = {
+    # 4097 objects in 5 x 13 groups: a ragged last tile, tiles straddling segments, slack slots
+    "static": dict(n_obj=4097, n_scenes=5, groups_per_scene=13, rec_rows=20),
+    "replay": dict(n_obj=3000, n_scenes=2, groups_per_scene=8, rec_rows=64),
+    "unused_row_fixed_point": dict(n_obj=3000, n_scenes=2, groups_per_scene=8, rec_rows=16, fixed_col0=1999),
+    # SetRecordInt on the guard cells in every window, Remove / AddRow / ClearRecord on the guard rows,
+    # with spawn, destroy and SwitchScene
+    "calls": dict(n_obj=3000, n_scenes=2, groups_per_scene=8, rec_rows=32, spawn_frac=0.02, destroy_frac=0.02,
+                  switch_frac=0.02, rec_set_frac=0.05, rec_set_float=False, rec_row_frac=0.03, cell_calls=0.15),
+}
+
+
+def _cell_guard_world(case, twin, n_ticks, seed, overrides=None):
+    assert twin in ("A", "B")
+    opt = dict(CELL_GUARD_CASES[case], **(overrides or {}))
+    fixed_col0, cell_calls = opt.pop("fixed_col0", None), opt.pop("cell_calls", 0.0)
+    w = make_world(n_ticks=n_ticks, seed=seed, records=True, ext_props="all", ext_frac=0.05, **opt)
+    cells, mirrors, progs = _cg_programs(case)
+    mpid = [PID[m] for m in mirrors]
+    rows = int(w["rec_rows"][0])
+    N = len(w["guid_head"])
+    rng = np.random.default_rng(seed + 4242)
+    if fixed_col0 is not None:
+        w["rec0_cells"][:, 0, :] = np.uint64(fixed_col0)
+    # the guard rows are used on about half the objects (make_world's masks never use row 63; objects
+    # created after the start keep their empty records)
+    for row in sorted({c[1] for c in cells}):
+        on = (rng.random(N) < 0.5) & ((w["born"] < 0) if "born" in w else True)
+        bit = np.uint64(1) << np.uint64(row)
+        w["rec0_used"] = np.where(on, w["rec0_used"] | bit, w["rec0_used"] & ~bit).astype(np.uint64)
+    # ---- programs: the guards on the mirrors (A) or on the cells (B) ----
+    ops = np.zeros((len(KINDS), MAX_OPS), OP_DTYPE)
+    n_ops = np.zeros(len(KINDS), np.int32)
+    for kind, lst in progs.items():
+        for i, (code, flags, dst, gd, a, b, c) in enumerate(lst):
+            if gd:
+                _, ci, cmp, kw = gd
+                if twin == "A":
+                    gd = guard(mpid[ci], cmp, **kw)
+                else:
+                    gd, flags = guard_cell(*cells[ci], cmp, **kw), flags | GUARD_CELL
+            ops[KID[kind], i] = (code, flags, dst, gd, a, b, c)
+        n_ops[KID[kind]] = len(lst)
+    w["ops"], w["n_ops"] = ops, n_ops
+    # ---- the random SetProperty calls skip the mirrors ----
+    keep = ~np.isin(w["x_pid"], mpid)
+    for k in ("x_tick", "x_obj", "x_pid", "x_bits"):
+        w[k] = w[k][keep]
+    born = w["born"] if "born" in w else np.full(N, -1, np.int32)
+    died = np.full(N, 1 << 30, np.int64)
+    if "d_tick" in w:
+        died[w["d_obj"]] = w["d_tick"]
+    # ---- SetRecordInt calls on the guard cells, every window: rows used or not, values the cell
+    #      already holds (the same value again in the next window, and twice in one window) ----
+    if cell_calls > 0:
+        rt, ro, rr, rc, rb = [], [], [], [], []
+        prev = None
+        for t in range(1, n_ticks):
+            alive = np.nonzero(((born < 0) | (born <= t)) & (t <= died))[0]
+            o = rng.choice(alive, size=max(1, int(cell_calls * len(alive))))
+            ci = rng.integers(0, len(cells), len(o))
+            v = np.where(rng.random(len(o)) < 0.3, 0, rng.integers(0, 3000, len(o))).astype(np.uint64)
+            if prev is not None:   # what the last window set, again (the objects still alive)
+                po, pc, pv = prev
+                ok = t <= died[po]
+                o, ci, v = np.concatenate([o, po[ok]]), np.concatenate([ci, pc[ok]]), np.concatenate([v, pv[ok]])
+            twice = rng.random(len(o)) < 0.2
+            o, ci, v = (np.concatenate([x, x[twice]]) for x in (o, ci, v))
+            prev = (o[:len(o) // 3], ci[:len(o) // 3], v[:len(o) // 3])
+            cr = np.array([c[1] for c in cells])[ci]
+            cc = np.array([c[2] for c in cells])[ci]
+            rt.append(np.full(len(o), t)), ro.append(o), rr.append(cr), rc.append(cc), rb.append(v)
+        cat = lambda a, b, dt: np.concatenate([a] + b).astype(dt)
+        n_add = sum(len(x) for x in rt)
+        tick = cat(w["r_tick"], rt, np.int32)
+        order = np.argsort(tick, kind="stable")   # behind the window's other record calls
+        w["r_tick"] = tick[order]
+        w["r_obj"] = cat(w["r_obj"], ro, np.int32)[order]
+        w["r_rec"] = cat(w["r_rec"], [np.zeros(n_add)], np.int32)[order]
+        w["r_row"] = cat(w["r_row"], rr, np.int32)[order]
+        w["r_col"] = cat(w["r_col"], rc, np.int32)[order]
+        w["r_bits"] = cat(w["r_bits"], rb, np.uint64)[order]
+        if "r_op" in w:
+            w["r_op"] = cat(w["r_op"], [np.zeros(n_add)], np.uint8)[order]
+            w["r_vals"] = np.concatenate([w["r_vals"], np.zeros((n_add, MAX_REC_COLS), np.uint64)])[order]
+    # ---- the mirrors: creation values, then one SetPropertyInt per window and mirror whose cell's
+    #      GetInt value the window's record calls changed (the used masks replayed call by call) ----
+    used = w["rec0_used"].astype(np.uint64).copy()
+    for ci, (_, row, col) in enumerate(cells):
+        on = ((used >> np.uint64(row)) & np.uint64(1)).astype(bool)
+        w["init_i"][mpid[ci]] = np.where(on, w["rec0_cells"][:, col, row].view(np.int64), 0)
+    if "r_tick" in w:
+        um = [int(x) for x in used]
+        rowm = (1 << rows) - 1
+        by_row = {}
+        for ci, (_, row, col) in enumerate(cells):
+            by_row.setdefault(row, []).append((ci, col))
+        r_op = w["r_op"] if "r_op" in w else np.zeros(len(w["r_tick"]), np.uint8)
+        xt, xo, xp, xb = [], [], [], []
+        for t in range(1, n_ticks):
+            final = {}   # (object, cell) -> the GetInt value the window's calls leave
+
+            def unuse(o, row):
+                if (um[o] >> row) & 1:
+                    um[o] &= ~(1 << row)
+                    for ci, _ in by_row.get(row, ()):
+                        final[(o, ci)] = 0
+            for i in np.nonzero(w["r_tick"] == t)[0]:
+                o, row, col, op = int(w["r_obj"][i]), int(w["r_row"][i]), int(w["r_col"][i]), int(r_op[i])
+                if op == 0:      # SetRecordInt: refused on an unused row (RC:194)
+                    if (um[o] >> row) & 1:
+                        for ci, c in by_row.get(row, ()):
+                            if c == col:
+                                final[(o, ci)] = int(w["r_bits"][i])
+                elif op == 1:    # AddRow: the first unused row (-1), or the given one (covered)
+                    if row < 0:
+                        free = ~um[o] & rowm
+                        if not free:
+                            continue
+                        row = (free & -free).bit_length() - 1
+                    um[o] |= 1 << row
+                    for ci, c in by_row.get(row, ()):
+                        final[(o, ci)] = int(w["r_vals"][i, c])
+                elif op == 2:
+                    unuse(o, row)
+                else:            # ClearRecord
+                    for r in range(rows):
+                        unuse(o, r)
+            for (o, ci), v in sorted(final.items()):
+                xt.append(t), xo.append(o), xp.append(mpid[ci]), xb.append(v)
+        tick = np.concatenate([w["x_tick"], np.array(xt, np.int32)]).astype(np.int32)
+        order = np.argsort(tick, kind="stable")
+        w["x_tick"] = tick[order]
+        w["x_obj"] = np.concatenate([w["x_obj"], np.array(xo, np.int32)]).astype(np.int32)[order]
+        w["x_pid"] = np.concatenate([w["x_pid"], np.array(xp, np.int32)]).astype(np.int32)[order]
+        w["x_bits"] = np.concatenate([w["x_bits"], np.array(xb, np.uint64)]).astype(np.uint64)[order]
+    w["cg_cells"] = np.array(cells, np.int32)
+    w["cg_mirrors"] = np.array(mpid, np.int32)
     return w
 
 
