@@ -23,7 +23,9 @@ constexpr int kRrcSitShift = 26;
 
 // device error word bits (Ctrl::err); kErrRemain: a fired heartbeat's remain was read from an LDS slot
 // this launch never wrote (only with kAblCheckRem)
-constexpr unsigned kErrMsgCap = 4, kErrTouch = 8, kErrFanBound = 16, kErrRemain = 32;
+// kErrRankWait: a rank workgroup of k_tick gave up waiting for a tile's counts (nfgpu_tick.hpp); the
+// frame's ranks and totals were not written
+constexpr unsigned kErrMsgCap = 4, kErrTouch = 8, kErrFanBound = 16, kErrRemain = 32, kErrRankWait = 64;
 
 // Control block: frame totals written by k_scan_tiles, byte tallies accumulated across frames,
 // the error word is sticky until nfk_summary_get clears it.  msg_extent = end of the last tile's
@@ -82,10 +84,8 @@ typedef uint32_t u32x2_a4 __attribute__((ext_vector_type(2), aligned(4)));
 // on the same HBM channel.
 constexpr int64_t kColPad = 2304;
 constexpr unsigned kAblScanInFrame = 131072;  // k_scan_tiles in every frame, not on first read
-constexpr unsigned kAblScanKernel = 1u << 28;  // dense ranks by k_scan_tiles in small worlds too (outputs exact)
-// k_tick ranks its own tiles up to this many (one agent-scope add per tile on one address: they
-// serialise at ~7 ns each, profiles/r08s_last_arrival_ranks_ab.txt, so only small worlds gain)
-constexpr int kLbMaxTiles = 256;
+constexpr unsigned kAblScanKernel = 1u << 28;  // dense ranks by k_scan_tiles for every world (outputs exact)
+constexpr unsigned kAblRankPer1 = 1u << 23;  // test hook: k_tick's rank workgroups take one count per thread and pass (outputs exact)
 constexpr unsigned kAblNoFuse = 4096;  // fan-out in k_fanout instead of k_tick's tail (outputs stay exact)
 // a check, outputs exact: k_tick marks every kind's remain slot (s_rem) unwritten at its start and
 // raises kErrRemain when the fired list reads one for a counted heartbeat that the schedule scan
@@ -310,12 +310,11 @@ struct Dev {
     uint32_t* fi_base; // [n_tiles + 1]
     uint32_t* re_base; // [n_rtiles + 1]
     uint32_t* msg_base;// [n_tiles + n_rtiles + 1] first message of each tile (k_scan_tiles)
-    // lb_rank (small worlds): k_tick writes ev_base / fi_base / msg_base and the frame totals
-    // itself — its last tile to publish counts scans them (lb_st [n_tiles][4] count words tagged
-    // with lb_epoch, one epoch per launch; lb_cnt the arrivals; nfgpu_tick.hpp) — and no
-    // k_scan_tiles runs for the frame
+    // lb_rank != 0 (fused fan-out, no record ops): k_tick writes ev_base / fi_base / msg_base and the
+    // frame totals itself — its tiles publish their counts in lb_st ([2][cap / kTile] words tagged with
+    // lb_epoch, one epoch per launch) and kRankWgs extra workgroups of the launch scan them, lb_rank
+    // counts per thread and pass (nfgpu_tick.hpp) — and no k_scan_tiles runs for the frame
     uint64_t* lb_st;
-    uint32_t* lb_cnt;
     uint32_t lb_epoch;
     int32_t lb_rank;
     // msg_tcap > 0: k_tick writes its tile's fan-out itself, property tile t's messages at

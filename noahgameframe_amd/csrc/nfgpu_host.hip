@@ -268,7 +268,7 @@ struct World {
     hipFunction_t jit_fn = nullptr;
     hipFunction_t jit_chain_fn = nullptr;  // k_chain_u on the same policy
     int jit_waves = 0, jit_u = 0;
-    bool jit_lb = false;  // the specialisation keeps k_tick's in-kernel ranks (a world of <= kLbMaxTiles tiles)
+    bool jit_lb = false;  // the specialisation has k_tick's rank workgroups compiled in (JitSchema::kLb)
     std::string jit_msg = "not compiled";
 
     int32_t ticks = 0;
@@ -1130,12 +1130,10 @@ void build_jit(World* w) {
     // non-temporal hints (kNt* bits of nfgpu_tick.hpp); NFGPU_JIT_NT overrides the default
     uint32_t nt = kJitNtDefault;
     if (const char* en = getenv("NFGPU_JIT_NT")) nt = (uint32_t)strtoul(en, nullptr, 0);
-    // a world committed with more than kLbMaxTiles tiles does not rank in k_tick: that code is compiled
-    // out of its specialisation (NFGPU_JIT_LB=1 keeps it, for A/B).  By the slots in use, not the
-    // capacity: the drop-in reserves 1M slots whatever the world (Tutorial3's 10k objects rank in k_tick
-    // and skip k_scan_tiles); a world that grows past the bound later ranks by k_scan_tiles (Dev::lb_rank
-    // is decided per frame), one that shrinks below it keeps k_scan_tiles with this code compiled out
-    bool lb = ((int64_t)std::max(w->d.N, 1) + kTile - 1) / kTile <= kLbMaxTiles;
+    // a world whose frames never rank in k_tick (record ops: their counts come from k_records too; dense
+    // ranks by k_scan_tiles asked for with kAblScanKernel) has that code compiled out of its
+    // specialisation (NFGPU_JIT_LB=0 / 1 overrides, for A/B; Dev::lb_rank is decided per frame)
+    bool lb = !w->d.has_recops && !(w->d.ablate & kAblScanKernel);
     if (const char* el = getenv("NFGPU_JIT_LB")) lb = el[0] == '1';
     const std::string src = jit_schema_source(w->tab, w->d, spec, nt, lb);
     int dev = 0;
@@ -2246,8 +2244,7 @@ int nfk_commit(void* world) {
     ALLOC(d.fi_base, (nt + 1) * 4);
     ALLOC(d.re_base, (nrt + 1) * 4);
     ALLOC(d.msg_base, (nt + nrt + 1) * 4);
-    ALLOC(d.lb_st, std::min<size_t>(nt, kLbMaxTiles) * 4 * 8);
-    ALLOC(d.lb_cnt, 64);
+    ALLOC(d.lb_st, std::max<size_t>(nt, 1) * kRankWgs * 8);
     d.msg_cap = w->cfg.msg_capacity > 0 ? w->cfg.msg_capacity : (int64_t)cap * 32;
     if (d.msg_cap > 0xFFFFFFFFll) return fail(NFK_ERR_ARG, "msg_capacity must fit 32-bit offsets");
     ALLOC(d.ev_slot, ev_n * 4);
@@ -2361,8 +2358,7 @@ int nfk_commit(void* world) {
     HIPCHK(hipMemset(d.fi_base, 0, (nt + 1) * 4));
     HIPCHK(hipMemset(d.re_base, 0, (nrt + 1) * 4));
     HIPCHK(hipMemset(d.msg_base, 0, (nt + nrt + 1) * 4));
-    HIPCHK(hipMemset(d.lb_st, 0, std::min<size_t>(nt, kLbMaxTiles) * 4 * 8));
-    HIPCHK(hipMemset(d.lb_cnt, 0, 64));
+    HIPCHK(hipMemset(d.lb_st, 0, std::max<size_t>(nt, 1) * kRankWgs * 8));
     w->lb_epoch = 0;
     // creation-time values are now on the device
     for (auto& v : w->init_props) std::vector<uint64_t>().swap(v);
@@ -3334,9 +3330,11 @@ static int execute_frame(World* w, int64_t now_ms, bool calls_only) {
     if (!w->committed) return fail(NFK_ERR_STATE, "commit first");
     // a device error of an earlier frame (host-mapped, no device read): that frame's outputs are
     // incomplete, so no further frame runs until nfk_summary_get has reported and cleared it
-    if (const unsigned e = err_host_bits(w); e & (kErrFanBound | kErrTouch))
+    if (const unsigned e = err_host_bits(w); e & (kErrFanBound | kErrTouch | kErrRankWait))
         return fail(NFK_ERR_DEVICE, std::string("device error of an earlier frame: ") +
-                                        ((e & kErrFanBound) ? "a tile's fan-out exceeded its bound" : "touch list overflow") +
+                                        ((e & kErrFanBound) ? "a tile's fan-out exceeded its bound"
+                                         : (e & kErrTouch)  ? "touch list overflow"
+                                                            : "k_tick's rank workgroups gave up waiting") +
                                         " (nfk_summary_get reports and clears it)");
     using clk = std::chrono::steady_clock;
     const bool trace = getenv("NFGPU_TRACE_EXEC") != nullptr;  // host phases to stderr
@@ -3904,14 +3902,16 @@ static int execute_frame(World* w, int64_t now_ms, bool calls_only) {
     // a world whose programs guard on record cells (the cells are the last read-only slots): its
     // library kernels are the DynSchemaCells instantiations
     const bool cells = d.n_u > 0 && d.u_pid[d.n_u - 1] >= kCellPid;
-    // A small world with no record pipeline after k_tick: its last tile ranks the frame's tiles
-    // and the frame has no k_scan_tiles launch (profiles/r09a_*)
-    d.lb_rank = (d.fuse_fan && !d.has_recops && d.n_tiles && d.n_tiles <= kLbMaxTiles &&
-                 !(d.ablate & kAblScanKernel) && (!(use_u && w->jit_fn) || w->jit_lb)) ? 1 : 0;
+    // No record pipeline after k_tick: kRankWgs extra workgroups of its launch rank the frame's tiles
+    // and the frame has no k_scan_tiles launch (profiles/r19a_rank_workgroups_ab.txt).  Dev::lb_rank =
+    // the counts a rank thread takes per pass: one while a pass of one each covers the world
+    if (d.fuse_fan && !d.has_recops && d.n_tiles && !(d.ablate & kAblScanKernel) && (!(use_u && w->jit_fn) || w->jit_lb))
+        d.lb_rank = (d.n_tiles <= kTPB || (d.ablate & kAblRankPer1)) ? 1 : kRankPer;
+    else
+        d.lb_rank = 0;
     if (d.lb_rank) {
         if (++w->lb_epoch == 0xFFFFFFFFu) {  // (clear the tags before they could repeat)
-            HIPCHK(hipMemsetAsync(w->d.lb_st, 0, std::min<size_t>(w->obj_of_slot.size() / kTile, kLbMaxTiles) * 4 * 8,
-                                  w->stream));
+            HIPCHK(hipMemsetAsync(w->d.lb_st, 0, std::max<size_t>((size_t)d.cap / kTile, 1) * kRankWgs * 8, w->stream));
             w->lb_epoch = 1;
         }
         d.lb_epoch = w->lb_epoch;
@@ -4052,10 +4052,11 @@ static int execute_frame(World* w, int64_t now_ms, bool calls_only) {
         }
         // the variant whose register slots hold the frame's working set (no spills at 6 or more
         // waves per SIMD): this schema's own k_tick, else a generic instantiation
-        const dim3 g((unsigned)d.n_tiles), b(kTPB);
+        // (... and the rank workgroups after the tiles': Dev::lb_rank)
+        const dim3 g((unsigned)(d.n_tiles + (d.lb_rank ? kRankWgs : 0))), b(kTPB);
         if (jit) {
             void* args[] = {&d};
-            HIPCHK(hipModuleLaunchKernel(w->jit_fn, (unsigned)d.n_tiles, 1, 1, kTPB, 1, 1, (unsigned)lds, w->stream,
+            HIPCHK(hipModuleLaunchKernel(w->jit_fn, g.x, 1, 1, kTPB, 1, 1, (unsigned)lds, w->stream,
                                          args, nullptr));
         } else if (use_u && cells) {  // the library's instantiations with the guard-cell loads and replay
             if (d.n_u <= 8 && !(d.ablate & kAblWaves6))
@@ -4127,7 +4128,7 @@ static int execute_frame(World* w, int64_t now_ms, bool calls_only) {
     // built on the first read (nfk_summary_get, nfk_outputs_get, nfk_read_*).
     w->scan_pending = false;
     if (d.lb_rank) {
-        // (written by k_tick's last tile)
+        // (written by k_tick's rank workgroups)
     } else if (d.fuse_fan && (!d.has_recops || d.fuse_rec) && !(d.ablate & kAblScanInFrame)) {
         w->scan_pending = true;
         w->scan_dev = d;
@@ -4319,6 +4320,7 @@ int nfk_summary_get(void* world, nfk_summary* out) {
     if (c.err & kErrTouch) return fail(NFK_ERR_TOUCH, "device touch list overflow");
     if (c.err & kErrFanBound) return fail(NFK_ERR_STATE, "a tile's fan-out exceeded its bound");
     if (c.err & kErrRemain) return fail(NFK_ERR_STATE, "k_tick read a fired heartbeat's remain it never wrote");
+    if (c.err & kErrRankWait) return fail(NFK_ERR_DEVICE, "k_tick's rank workgroups gave up waiting for a tile's counts: the frame has no ranks");
     if (c.err & kErrMsgCap)
         return fail(NFK_ERR_CAPACITY, "device output capacity exceeded (err=" + std::to_string(c.err) + ")");
     return NFK_OK;
@@ -4332,9 +4334,10 @@ int nfk_outputs_get(void* world, nfk_outputs* o) {
     if (r) return r;
     // a device error of a frame that has completed (host-mapped word, no device read); a frame
     // still running reports through the next call that waits for it (nfk_execute, nfk_summary_get)
-    if (const unsigned e = err_host_bits(w); e & (kErrFanBound | kErrTouch))
+    if (const unsigned e = err_host_bits(w); e & (kErrFanBound | kErrTouch | kErrRankWait))
         return fail(NFK_ERR_DEVICE, (e & kErrFanBound) ? "a tile's fan-out exceeded its bound: the recipient lists are truncated"
-                                                       : "touch list overflow: events are missing");
+                                    : (e & kErrTouch)  ? "touch list overflow: events are missing"
+                                                       : "k_tick's rank workgroups gave up waiting: the frame has no ranks");
     r = ensure_ranks(w);  // (asynchronous, on the world's stream like the frame)
     if (r) return r;
     const Dev& d = w->d;
@@ -4634,7 +4637,7 @@ int nfk_read_frame(void* world, uint32_t what, nfk_frame_host* o) {
     Ctrl c;
     r = read_ctrl(w, &c);
     if (r) return r;
-    if (c.err & (kErrFanBound | kErrTouch))
+    if (c.err & (kErrFanBound | kErrTouch | kErrRankWait))
         return fail(NFK_ERR_DEVICE, "the frame's outputs are incomplete (device error " + std::to_string(c.err) + ")");
     if (c.msg_extent > (unsigned long long)w->d.msg_cap) return fail(NFK_ERR_CAPACITY, "fan-out not recovered");
     const Dev& d = w->d;
@@ -4946,7 +4949,9 @@ int nfk_jit_preview_rec(int32_t n_int, int32_t n_flt, int32_t n_class, int32_t n
     const char* es = getenv("NFGPU_JIT_SPEC");
     uint32_t nt = kJitNtDefault;
     if (const char* en = getenv("NFGPU_JIT_NT")) nt = (uint32_t)strtoul(en, nullptr, 0);
-    const std::string s = jit_schema_source(*tab, d, es && es[0] == '1', nt);
+    bool lb = true;  // (rank workgroups compiled in, as for a world without record ops; NFGPU_JIT_LB as at commit)
+    if (const char* el = getenv("NFGPU_JIT_LB")) lb = el[0] == '1';
+    const std::string s = jit_schema_source(*tab, d, es && es[0] == '1', nt, lb);
     copy_msg(s, src, src_cap);
     if (!compile) {
         *ok = 1;

@@ -197,8 +197,9 @@ struct DynSchemaT {
     static constexpr uint32_t kSpecMask = 0;  // operands loaded before the fire test (none)
     // non-temporal hints (kNt* bits): none in the library's instantiations
     static constexpr uint32_t kNt = 0;
-    // k_tick may rank a small world's tiles itself (Dev::lb_rank); a policy for a world of more than
-    // kLbMaxTiles tiles compiles that code out (kLb = false) and the frame ranks by k_scan_tiles
+    // k_tick may rank the frame's tiles itself (Dev::lb_rank: the tiles publish their counts, rank
+    // workgroups scan them); a policy of a world that never does (record ops, kAblScanKernel) compiles
+    // that code out (kLb = false) and its frames rank by k_scan_tiles
     static constexpr bool kLb = true;
     static constexpr int kNK = NFK_MAX_KINDS;  // (an upper bound only)
     // guard cells (NFK_GUARD_CELL): any U slot may hold one, told by its Dev::u_pid at run time
@@ -388,62 +389,112 @@ __device__ __forceinline__ uint32_t sched_scan(const Dev& d, int e, unsigned& by
     return fired;
 }
 
-// ---- dense ranks in k_tick (Dev::lb_rank, worlds of at most kLbMaxTiles tiles) ----
-// What k_scan_tiles computes, without its launch: every tile publishes its three counts (events,
-// fired, messages) at its block scan and counts itself in lb_cnt; the tile that arrives there last
-// computes ev_base / fi_base / msg_base and the frame totals of all tiles at its end and resets
-// lb_cnt for the next launch.  The counts are tagged with the launch's epoch (lb_st word:
-// epoch << 32 | value), so the last tile waits for a word not yet visible instead of fencing,
-// and nothing is cleared between launches.
+// ---- dense ranks in k_tick (Dev::lb_rank) ----
+// What k_scan_tiles computes, without its launch.  Every tile publishes its counts once its events
+// are written and before its fan-out (a store at the block scan itself, where the counts are first
+// known, splits the emission's code there and costs config[1]'s k_tick 9 us even when it never runs:
+// profiles/r19a_rank_workgroups_ab.txt): two words, (fired << 16 | events) and messages, each
+// tagged with the launch's epoch (lb_st word: epoch << 32 | value; plane q of the array holds word q
+// of every tile), stored as relaxed agent-scope atomics.  A tile reads nothing back and waits for
+// nothing.  kRankWgs extra workgroups of the same launch (blockIdx.x >= n_tiles) own no tile: rank
+// workgroup q polls plane q until every word carries this launch's epoch, scans the counts and writes
+// ev_base / fi_base (q = 0) or msg_base (q = 1) and the frame totals.  The word polled is the
+// payload, so the result does not depend on when or where a rank workgroup is dispatched: one
+// that starts early sleeps between polls in its slot, and no tile ever waits for it.  Nothing is
+// cleared between launches (the epoch changes).
+constexpr int kRankWgs = 2;
+constexpr int kRankPer = 16;  // counts per thread and pass (Dev::lb_rank; 4096 tiles in one pass)
+// a poll that has not seen its epoch after this long raises kErrRankWait (constant 100 MHz clock: 1 s)
+constexpr unsigned long long kRankWaitTicks = 100000000ull;
+
 __device__ __forceinline__ void lb_store(const Dev& d, int tile, int q, uint32_t v) {
-    __hip_atomic_store(d.lb_st + (size_t)tile * 4 + q, ((uint64_t)d.lb_epoch << 32) | v, __ATOMIC_RELAXED,
-                       __HIP_MEMORY_SCOPE_AGENT);
+    __hip_atomic_store(d.lb_st + (size_t)q * (size_t)(d.cap / kTile) + tile, ((uint64_t)d.lb_epoch << 32) | v,
+                       __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
-__device__ __forceinline__ uint32_t lb_load(const Dev& d, int tile, int q) {
-    const uint64_t* p = d.lb_st + (size_t)tile * 4 + q;
-    uint64_t s;
-    while (((s = __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) >> 32) != d.lb_epoch)
-        __builtin_amdgcn_s_sleep(1);
-    return (uint32_t)s;
+// threads 0 and 1 publish the tile's counts (events and fired fit 16 bits each: the block scan's fields)
+__device__ __forceinline__ void lb_publish(const Dev& d, int tile, uint32_t ev, uint32_t fi, uint32_t msg) {
+    if (threadIdx.x < 2) lb_store(d, tile, threadIdx.x, threadIdx.x == 0 ? (fi << 16) | ev : msg);
 }
-// threads 0..2 publish; returns (thread 0) whether this tile arrived last
-__device__ __forceinline__ bool lb_arrive(const Dev& d, int tile, uint32_t ev, uint32_t fi, uint32_t msg) {
-    if (threadIdx.x < 3) lb_store(d, tile, threadIdx.x, threadIdx.x == 0 ? ev : threadIdx.x == 1 ? fi : msg);
-    if (threadIdx.x != 0) return false;
-    return __hip_atomic_fetch_add(d.lb_cnt, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == (uint32_t)d.n_tiles - 1u;
-}
-// the whole workgroup of the last tile (n_tiles <= kLbMaxTiles = kTPB: one count per thread)
-__device__ void lb_scan_all(const Dev& d, unsigned long long* s_w) {
-    static_assert(kLbMaxTiles <= kTPB, "one tile's counts per thread");
+// One rank workgroup: passes of kTPB * kPer tiles with a carry.  Every load of a poll round is issued
+// before any is checked; stale words are polled again after a sleep.
+template <int kPer>
+__device__ void lb_rank_wg(const Dev& d, const int q, unsigned long long* s_w, unsigned& s_late) {
     const int n = d.n_tiles, t = (int)threadIdx.x;
-    uint32_t ev = 0, fi = 0, ms = 0;
-    if (t < n) {
-        ev = lb_load(d, t, 0);
-        fi = lb_load(d, t, 1);
-        ms = lb_load(d, t, 2);
-    }
-    unsigned long long tef, tm;
-    const unsigned long long xef = block_excl_scan(((unsigned long long)fi << 32) | ev, s_w, tef);
+    if (t == 0) s_late = 0;
     __syncthreads();
-    block_excl_scan(ms, s_w, tm);
-    if (t < n) {
-        d.ev_base[t] = (uint32_t)xef;
-        d.fi_base[t] = (uint32_t)(xef >> 32);
-        d.msg_base[t] = (uint32_t)t * d.msg_tcap;
+    const uint64_t* const p = d.lb_st + (size_t)q * (size_t)(d.cap / kTile);
+    unsigned long long carry = 0;
+    for (int c0 = 0; c0 < n; c0 += kTPB * kPer) {
+        const int i0 = c0 + t * kPer;
+        uint64_t x[kPer];
+        uint32_t stale = 0;
+#pragma unroll
+        for (int j = 0; j < kPer; j++) {
+            x[j] = (uint64_t)d.lb_epoch << 32;  // (a tile past n_tiles: count 0)
+            if (i0 + j < n) stale |= 1u << j;
+        }
+        bool late = false;
+        const unsigned long long t0 = __builtin_amdgcn_s_memrealtime();
+        while (stale) {
+#pragma unroll
+            for (int j = 0; j < kPer; j++)
+                if ((stale >> j) & 1u) x[j] = __hip_atomic_load(p + i0 + j, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+#pragma unroll
+            for (int j = 0; j < kPer; j++)
+                if ((uint32_t)(x[j] >> 32) == d.lb_epoch) stale &= ~(1u << j);
+            if (!stale) break;
+            if (__builtin_amdgcn_s_memrealtime() - t0 > kRankWaitTicks) {
+                late = true;
+                break;
+            }
+            __builtin_amdgcn_s_sleep(8);
+        }
+        // (a barrier every thread reaches: a wave that gave up takes the workgroup out, no rank written)
+        if (late) s_late = 1;
+        __syncthreads();
+        if (s_late) {
+            if (late) dev_error(d, kErrRankWait);
+            return;
+        }
+        unsigned long long sum = 0;
+#pragma unroll
+        for (int j = 0; j < kPer; j++) {
+            const uint32_t v = (uint32_t)x[j];
+            x[j] = q == 0 ? ((unsigned long long)(v >> 16) << 32) | (v & 0xFFFFu) : v;
+            sum += x[j];
+        }
+        unsigned long long tot;
+        unsigned long long run = carry + block_excl_scan(sum, s_w, tot);
+#pragma unroll
+        for (int j = 0; j < kPer; j++) {
+            if (i0 + j < n) {
+                if (q == 0) {
+                    d.ev_base[i0 + j] = (uint32_t)run;
+                    d.fi_base[i0 + j] = (uint32_t)(run >> 32);
+                } else {
+                    d.msg_base[i0 + j] = (uint32_t)(i0 + j) * d.msg_tcap;  // (fixed-stride runs)
+                }
+            }
+            run += x[j];
+        }
+        carry += tot;
+        __syncthreads();  // (s_w is reused by the next pass)
     }
     if (t == 0) {  // (k_scan_tiles' totals; no record tiles in such a frame)
-        const unsigned long long ext = (unsigned long long)n * d.msg_tcap;
-        d.ev_base[n] = (uint32_t)tef;
-        d.fi_base[n] = (uint32_t)(tef >> 32);
-        d.msg_base[n] = (uint32_t)ext;
-        d.re_base[0] = 0;
-        d.ctrl->n_ev = (uint32_t)tef;
-        d.ctrl->n_fi = (uint32_t)(tef >> 32);
-        d.ctrl->n_re = 0;
-        d.ctrl->msg_extent = ext;
-        d.ctrl->n_msgs_ptiles = tm;
-        if (ext > (unsigned long long)d.msg_cap || (d.ablate & kAblForceMsgCap)) dev_error(d, kErrMsgCap);
-        __hip_atomic_store(d.lb_cnt, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // (every tile has arrived)
+        if (q == 0) {
+            d.ev_base[n] = (uint32_t)carry;
+            d.fi_base[n] = (uint32_t)(carry >> 32);
+            d.re_base[0] = 0;
+            d.ctrl->n_ev = (uint32_t)carry;
+            d.ctrl->n_fi = (uint32_t)(carry >> 32);
+            d.ctrl->n_re = 0;
+        } else {
+            const unsigned long long ext = (unsigned long long)n * d.msg_tcap;
+            d.msg_base[n] = (uint32_t)ext;
+            d.ctrl->msg_extent = ext;
+            d.ctrl->n_msgs_ptiles = carry;
+            if (ext > (unsigned long long)d.msg_cap || (d.ablate & kAblForceMsgCap)) dev_error(d, kErrMsgCap);
+        }
     }
 }
 
@@ -455,8 +506,7 @@ __device__ void lb_scan_all(const Dev& d, unsigned long long* s_w) {
 // program destination joins that slot's diff (frame-start value = the group's x_old), a Set of any
 // other property is a "standalone" event (x_old -> x_new) merged into the entity's events in
 // property-id order.  Outputs of tile t are written densely at [t * tile_cap, t * tile_cap + count);
-// k_scan_tiles, or in a small world this kernel's last tile (Dev::lb_rank), turns the counts into
-// global ranks.
+// k_scan_tiles, or this kernel's rank workgroups (Dev::lb_rank), turn the counts into global ranks.
 // kWPE: waves per SIMD the register allocation aims at.  The LDS image of the frame-start values
 // is dynamic: n_w writable slots x kTPB.
 // Dev::xcd_map: workgroup b (dealt to XCD b mod 8) -> a tile of that XCD's contiguous range
@@ -468,7 +518,7 @@ __device__ __forceinline__ int xcd_tile(int b, int n) {
 // One tile of k_tick (the workgroup's; its LDS passed in).
 template <int kU, class S>
 __device__ __forceinline__ void tick_tile(const Dev& d, const int tile, unsigned long long* s_w, unsigned& s_bytes,
-                                          uint32_t& s_lb_last, uint32_t* s_pb, uint64_t* s_o) {
+                                          uint32_t* s_pb, uint64_t* s_o) {
     constexpr int kW = kU < kMaxW ? kU : kMaxW;  // writable register slots
     const int e = tile * kTile + (int)threadIdx.x;
     if (d.tile_work && !d.tile_work[tile]) {  // (block-uniform) a calls-only pass, no Set group here:
@@ -478,12 +528,7 @@ __device__ __forceinline__ void tick_tile(const Dev& d, const int tile, unsigned
             d.t_fi[tile] = 0;
             d.t_msg[tile] = 0;
         }
-        if (S::kLb && d.lb_rank) {
-            const bool last = lb_arrive(d, tile, 0u, 0u, 0u);
-            if (threadIdx.x == 0) s_lb_last = last;
-            __syncthreads();
-            if (s_lb_last) lb_scan_all(d, s_w);
-        }
+        if (S::kLb && d.lb_rank) lb_publish(d, tile, 0u, 0u, 0u);
         return;
     }
     const bool fuse = d.msg_tcap != 0;  // this tile's fan-out is written here, at tile * msg_tcap
@@ -654,8 +699,7 @@ __device__ __forceinline__ void tick_tile(const Dev& d, const int tile, unsigned
             atomicMax(&s_pb[2], nmax);
         }
     }
-    // this tile's counts for the dense ranks; whether it is the last to publish them (thread 0)
-    const bool lb_last = S::kLb && d.lb_rank && lb_arrive(d, tile, (unsigned)((tot >> 32) & 0xFFFF), (unsigned)(tot >> 48), tmsg);
+    // this tile's counts for the dense ranks, as early as they are known (the rank workgroups poll them)
     // this tile's output runs (wave-uniform bases, tile-local 32-bit offsets)
     const size_t ev0 = (size_t)tile * d.ev_tcap, fi0 = (size_t)tile * d.fi_tcap;
     uint32_t* const t_evm = d.ev_moff + ev0;
@@ -797,6 +841,8 @@ __device__ __forceinline__ void tick_tile(const Dev& d, const int tile, unsigned
         const unsigned tev = (unsigned)((tot >> 32) & 0xFFFF);
         const bool fan = tmsg && tmsg <= d.msg_tcap;
         if (tmsg > d.msg_tcap && threadIdx.x == 0) dev_error(d, kErrFanBound);  // (host bound)
+        // this tile's counts for the dense ranks (the rank workgroups poll them while the fan-out runs)
+        if (S::kLb && d.lb_rank) lb_publish(d, tile, tev, (unsigned)(tot >> 48), tmsg);
         // No per-event message offsets: the tile's run holds its events' recipients in event order
         // (the readers count through it: k_counted_moff)
         if (fan) {
@@ -943,28 +989,31 @@ __device__ __forceinline__ void tick_tile(const Dev& d, const int tile, unsigned
     // tile counts and algorithmic-byte tally
     const unsigned wb = (unsigned)wave_sum(bytes);
     if ((threadIdx.x & 63) == 0) atomicAdd(&s_bytes, wb);
-    if (S::kLb && threadIdx.x == 0) s_lb_last = lb_last;
     __syncthreads();
-    const bool lb_scan = S::kLb && d.lb_rank && s_lb_last;
     if (threadIdx.x == 0) {
         d.t_ev[tile] = (unsigned)((tot >> 32) & 0xFFFF);
         d.t_fi[tile] = (unsigned)(tot >> 48);
         d.t_msg[tile] = (unsigned)tot;
         tally_add(d, kTallyTick, (unsigned long long)(s_bytes + 12 + (fuse ? 16 : 0)));
     }
-    if constexpr (S::kLb)
-        if (lb_scan) lb_scan_all(d, s_w);
 }
 
 template <int kWPE, int kU, class S = DynSchema>
 __global__ __launch_bounds__(kTPB) __attribute__((amdgpu_waves_per_eu(kWPE, 8))) void k_tick(Dev d) {
     __shared__ unsigned long long s_w[kTPB / 64];
     __shared__ unsigned s_bytes;
-    __shared__ uint32_t s_lb_last;  // this tile ranks the frame's tiles (Dev::lb_rank)
     __shared__ uint32_t s_pb[3];   // pl_slot run of the groups with dirty events [lo, hi), most recipients
     extern __shared__ __align__(16) uint64_t s_o[];  // [n_w][kTPB] frame-start values of the writable slots
+    if constexpr (S::kLb) {
+        if ((int)blockIdx.x >= d.n_tiles) {  // a rank workgroup (Dev::lb_rank counts per thread and pass)
+            const int q = (int)blockIdx.x - d.n_tiles;
+            if (d.lb_rank == 1) lb_rank_wg<1>(d, q, s_w, s_bytes);  // (s_bytes: a tile's tally, free here)
+            else lb_rank_wg<kRankPer>(d, q, s_w, s_bytes);
+            return;
+        }
+    }
     const int tile = d.xcd_map ? xcd_tile((int)blockIdx.x, d.n_tiles) : (int)blockIdx.x;
-    tick_tile<kU, S>(d, tile, s_w, s_bytes, s_lb_last, s_pb, s_o);
+    tick_tile<kU, S>(d, tile, s_w, s_bytes, s_pb, s_o);
 }
 
 
