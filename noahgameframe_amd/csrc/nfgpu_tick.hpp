@@ -862,11 +862,81 @@ __device__ __forceinline__ void tick_tile(const Dev& d, const int tile, unsigned
             uint32_t* s_win = s_ev + 3u * ecap;
             uint32_t* s_pl = s_ev + (R - npl);
             uint32_t* out = d.msg_rcpt + mb;
-            if (staged) {
-                for (uint32_t i = threadIdx.x; i < npl; i += kTPB) s_pl[i] = (uint32_t)d.pl_slot[pb_lo + i];
+            const bool direct = win && staged && !(d.ablate & kAblFanTriples) && tmsg <= ((R - npl) & ~3u);
+            if (staged) {  // (the tally counts the run once for a direct tile too: summaries do not depend on the path)
+                if (!direct)
+                    for (uint32_t i = threadIdx.x; i < npl; i += kTPB) s_pl[i] = (uint32_t)d.pl_slot[pb_lo + i];
                 bytes += 4 * ((npl + kTPB - 1 - threadIdx.x) / kTPB);
             }
             bytes += 4 * nmsg;
+            // Short runs whose tile's whole run would fit beside the staged players: no triples, no
+            // event loop and no window passes.  A thread knows its own events and their message
+            // offsets, so it writes their recipients straight into the window [0, tmsg) at s_o
+            // (tile-local offsets), and the window is stored once.  The players are read from
+            // pl_slot through L1 (a group's run is read by its ~250 neighbouring threads), which
+            // saves the staging and its barrier.  Block-uniform; NFGPU_ABLATE kAblFanTriples keeps
+            // the triples for every tile.
+            if (direct) {
+                uint32_t* const s_run = (uint32_t*)s_o;
+                if (nsd) {  // (rare) the merged walk gives each event's offset and recipients
+                    walk([&](unsigned, unsigned m, uint32_t, int, int, EvFan f) {
+                        uint32_t* w = s_run + pmsg0 + m;
+                        if (!f.pub) {
+                            if (f.n) w[0] = (uint32_t)e;
+                            return;
+                        }
+                        const auto* pl = d.pl_slot + (uint32_t)desc;
+                        for (uint32_t k = 0; k < f.n; k++) w[k] = (uint32_t)pl[k + ((r1 && k + 1 >= r1) ? 1u : 0u)];
+                    });
+                } else if (nmsg) {
+                    // public events with recipients: the q-th one's run starts npub * q + (the
+                    // private events before it: 4 bits each in pk) words after the thread's first
+                    const uint32_t dpub = npub ? dm & pubm : 0u, dprv = dm & privm;
+                    unsigned long long pk = 0;
+                    if (dprv) {  // a private event goes to the entity itself
+#pragma unroll
+                        for (int j = 0; j < kW; j++) {
+                            if (j >= S::n_w(d)) continue;
+                            const uint32_t below = dm & S::u_lower(d, j);
+                            const uint32_t q = __builtin_popcount(below & pubm), pv = __builtin_popcount(below & privm);
+                            if ((dprv >> j) & 1) s_run[pmsg0 + npub * q + pv] = (uint32_t)e;
+                            pk |= ((dpub >> j) & 1) ? (unsigned long long)pv << (4u * q) : 0ull;
+                        }
+                    }
+                    const uint32_t npe = __builtin_popcount(dpub);
+                    if (npe) {
+                        // eight recipients at a time, read once and written to every public event's
+                        // run: a store past a run's end repeats its last word (the same value at the
+                        // same place), so only the event loop's trip count differs between lanes
+                        const auto* pl = d.pl_slot + (uint32_t)desc;
+#pragma unroll 1
+                        for (uint32_t k0 = 0; k0 < nm; k0 += 8) {  // uniform
+                            uint32_t x[8], o[8];
+#pragma unroll
+                            for (int k = 0; k < 8; k++) {  // every player of the group but self
+                                o[k] = min(k0 + (uint32_t)k, npub - 1u);
+                                x[k] = (uint32_t)pl[o[k] + ((r1 && o[k] + 1 >= r1) ? 1u : 0u)];
+                            }
+                            uint32_t* w = s_run + pmsg0;
+                            unsigned long long t = pk;
+                            for (uint32_t q = 0; q < npe; q++) {
+                                uint32_t* wq = w + ((uint32_t)t & 15u);
+#pragma unroll
+                                for (int k = 0; k < 8; k++) wq[o[k]] = x[k];
+                                w += npub;
+                                t >>= 4;
+                            }
+                        }
+                    }
+                }
+                __syncthreads();
+                // mb is a multiple of 4 (msg_tcap is): 16-byte stores; nothing refills the window
+                const uint32_t n4 = tmsg >> 2;
+                uint4* dst4 = (uint4*)out;
+                const uint4* src4 = (const uint4*)s_run;
+                for (uint32_t i = threadIdx.x; i < n4; i += kTPB) st_nt<(S::kNt & kNtFanStore) != 0>(dst4 + i, src4[i]);
+                if (threadIdx.x < (tmsg & 3u)) out[4 * n4 + threadIdx.x] = s_run[4 * n4 + threadIdx.x];
+            } else  // chunks of event triples (the code below keeps its indentation)
             for (unsigned c0 = 0; c0 < tev; c0 += ecap) {  // uniform
                 const unsigned c1 = min(tev, c0 + ecap);
                 // a runtime loop over the slots (an unrolled one gets hoisted out of the chunk loop
