@@ -61,22 +61,6 @@ struct alignas(16) SchedCold {
     float interval;  // mfIntervalTime
 };
 
-// timing-only ablations (NFGPU_ABLATE env var); outputs are wrong when set
-constexpr unsigned kAblPrograms = 4;
-constexpr unsigned kAblPerKind = 8;  // not an ablation: force the per-kind operand path (outputs stay exact)
-constexpr unsigned kAblWaves6 = 16, kAblWaves8 = 32;  // k_tick register budgets (outputs stay exact)
-constexpr unsigned kAblWaves5 = 8192;                  // (6 is the default)
-constexpr unsigned kAblNoRun = 512, kAblNoLoads = 1024, kAblNoEmit = 2048;  // timing only (k_tick)
-constexpr unsigned kAblNoWriteBack = 1u << 18, kAblNoSchedStore = 1u << 19;  // timing only (k_tick)
-constexpr unsigned kAblNoFiStore = 128, kAblNoEvStore = 256;  // timing only (k_tick): no fired-list / event-array stores
-constexpr unsigned kAblGroupColumns = 1u << 20, kAblSigGroups = 1u << 21;  // column layouts (outputs exact)
-constexpr unsigned kAblNoPad = 1u << 22;  // columns / schedule kinds at power-of-two strides (outputs exact)
-constexpr unsigned kAblFanWin16 = 1u << 24, kAblFanWin32 = 1u << 25;  // k_tick fan-out LDS window up to 16 / 32 recipients (outputs exact)
-constexpr unsigned kAblFan1 = 1u << 26;      // k_tick fan-out: one recipient per lane (the round-1 form; outputs exact)
-constexpr unsigned kAblFanNoWin = 1u << 30;  // k_tick fan-out: lane groups for every run length, no LDS window (outputs exact)
-constexpr unsigned kAblFanTriples = 1u << 16;  // k_tick fan-out: short runs through the event triples and window passes for every tile, no direct window (outputs exact)
-constexpr unsigned kAblTinyTcap = 1u << 27;  // test hook: k_tick's fan-out bound set to 4 messages (kErrFanBound)
-constexpr unsigned kAblForceMsgCap = 1u << 29;  // test hook: the frame's ranks also raise kErrMsgCap
 // four u32 at a dword-aligned address (gfx950 global memory allows it; one 16-byte store)
 typedef uint32_t u32x4_a4 __attribute__((ext_vector_type(4), aligned(4)));
 typedef uint32_t u32x2_a4 __attribute__((ext_vector_type(2), aligned(4)));
@@ -84,10 +68,22 @@ typedef uint32_t u32x2_a4 __attribute__((ext_vector_type(2), aligned(4)));
 // two, unpadded columns sit exactly 2^k bytes apart and one entity's values of every column fall
 // on the same HBM channel.
 constexpr int64_t kColPad = 2304;
-constexpr unsigned kAblScanInFrame = 131072;  // k_scan_tiles in every frame, not on first read
-constexpr unsigned kAblScanKernel = 1u << 28;  // dense ranks by k_scan_tiles for every world (outputs exact)
-constexpr unsigned kAblRankPer1 = 1u << 23;  // test hook: k_tick's rank workgroups take one count per thread and pass (outputs exact)
-constexpr unsigned kAblNoFuse = 4096;  // fan-out in k_fanout instead of k_tick's tail (outputs stay exact)
+
+// The switches of NFGPU_ABLATE (an environment variable read once per world, at nfk_commit:
+// Dev::ablate).  Tests and tools name the bits by number; a retired bit is not used again
+// (16, 8192, 1 << 17, 1 << 20, 1 << 21, 1 << 22, 1 << 26 and 1 << 30 are retired).
+// -- timing only: outputs are invalid when set (tools/ablate.py, tools/pmc_mix.sh) --
+constexpr unsigned kAblPrograms = 4;
+constexpr unsigned kAblNoFiStore = 128, kAblNoEvStore = 256;  // k_tick: no fired-list / event-array stores
+constexpr unsigned kAblNoRun = 512, kAblNoLoads = 1024, kAblNoEmit = 2048;  // k_tick
+constexpr unsigned kAblNoWriteBack = 1u << 18, kAblNoSchedStore = 1u << 19;  // k_tick
+// -- exact variants, kept for A/B and as the tests' references: outputs stay exact --
+constexpr unsigned kAblPerKind = 8;   // force the per-kind operand path
+constexpr unsigned kAblWaves8 = 32;   // k_tick's LDS share, and the hipRTC build's register budget, as at 8 waves per SIMD
+constexpr unsigned kAblNoFuse = 4096;  // fan-out in k_fanout instead of k_tick's tail
+constexpr unsigned kAblFanTriples = 1u << 16;  // k_tick fan-out: short runs through the event triples and window passes for every tile, no direct window
+constexpr unsigned kAblFanWin16 = 1u << 24, kAblFanWin32 = 1u << 25;  // k_tick fan-out LDS window up to 16 / 32 recipients
+constexpr unsigned kAblScanKernel = 1u << 28;  // dense ranks by k_scan_tiles for every world
 // a check, outputs exact: k_tick marks every kind's remain slot (s_rem) unwritten at its start and
 // raises kErrRemain when the fired list reads one for a counted heartbeat that the schedule scan
 // did not write (a counted heartbeat's remain is >= 0 after a fire; a forever one's may be the
@@ -95,6 +91,10 @@ constexpr unsigned kAblNoFuse = 4096;  // fan-out in k_fanout instead of k_tick'
 // hipRTC fired-list corruption read such slots: DESIGN.md §3)
 constexpr unsigned kAblCheckRem = 64;
 constexpr int32_t kRemUnset = (int32_t)0x80000001;
+// -- test hooks --
+constexpr unsigned kAblRankPer1 = 1u << 23;  // k_tick's rank workgroups take one count per thread and pass (outputs exact)
+constexpr unsigned kAblTinyTcap = 1u << 27;  // k_tick's fan-out bound set to 4 messages (kErrFanBound)
+constexpr unsigned kAblForceMsgCap = 1u << 29;  // the frame's ranks also raise kErrMsgCap
 
 // Where row r of a record sits in its slot's [rows] vector of one column: the used rows first, in
 // row order, then the unused rows in row order (a stable partition by the used-row mask, so the
@@ -173,9 +173,8 @@ __host__ __device__ __forceinline__ bool guard_ok(uint32_t cmp, int64_t g, int64
 struct Tables {
     nfk_op ops[NFK_MAX_KINDS][NFK_MAX_OPS];
     OpX opx[NFK_MAX_KINDS][NFK_MAX_OPS];
-    // property storage: property p of slot e is the 64-bit word pmem[p_off[p] + e * p_str[p]].
-    // Properties that one heartbeat program touches together share a column group stored
-    // interleaved ([cap][group size]), so a sparse heartbeat reads one line per entity.
+    // property storage: property p of slot e is the 64-bit word pmem[p_off[p] + e * p_str[p]]: one
+    // plain column per int / float property (stride 1), one 16-byte column per object property (2)
     int64_t p_off[kMaxProps];
     int32_t p_str[kMaxProps];
     uint32_t umask[NFK_MAX_KINDS];                 // kind k's U slots: writable bits | read-only indices << 16
@@ -329,9 +328,6 @@ struct Dev {
     int32_t fuse_rec;
     uint32_t msg_rb0, msg_rtcap;
     int32_t lds_words; // k_tick's dynamic LDS in 4-byte words (message window + staged players)
-    // xcd_map: k_tick's workgroup b runs tile xcd_tile(b): the workgroups the dispatcher deals to
-    // one XCD (b mod 8) take one contiguous range of tiles (their L2 holds neighbouring tiles)
-    int32_t xcd_map;
     // outputs (tile-staged)
     uint32_t* ev_slot; uint32_t* ev_pid; uint64_t* ev_old; uint64_t* ev_new; uint32_t* ev_moff;
     uint32_t* fi_slot; uint32_t* fi_kind; int32_t* fi_remain;

@@ -924,10 +924,6 @@ int grow_event_tiles(World* w, int64_t per_tile) {
     return NFK_OK;
 }
 
-// The programs' working set: program destinations -> writable U slots [0, n_w) and the operands
-// programs only read -> slots [n_w, n_u), each group in property-id order; the tables name
-// read-only operand r as 0x80 | r.  Fills the kinds' U-slot tables (opu, umask, opx, w_slot);
-// false when the set does not fit k_tick's register slots (k_tick_touch runs instead).
 // the record-event tiles grown for a frame whose SetRecord groups add events beside the record
 // programs' (contents dropped: called before the frame writes them)
 int grow_rec_tiles(World* w, int64_t per_tile) {
@@ -954,6 +950,10 @@ static bool prop_op(int code) {
            code == NFK_OP_FSET;
 }
 
+// The programs' working set: program destinations -> writable U slots [0, n_w) and the operands
+// programs only read -> slots [n_w, n_u), each group in property-id order; the tables name
+// read-only operand r as 0x80 | r.  Fills the kinds' U-slot tables (opu, umask, opx, w_slot);
+// false when the set does not fit k_tick's register slots (k_tick_touch runs instead).
 bool build_u_tables(Tables& tab, int NK, std::vector<int>& wp, std::vector<int>& rp) {
     bool u_ok = false;
     {
@@ -1088,7 +1088,6 @@ void set_working_set(World* w) { fill_u_dev(w->d, w->tab, w->u_wp, w->u_rp, w->u
 
 // waves per SIMD k_tick's register budget aims at, by the working set's size
 int tick_waves(int n_u, uint32_t ablate) {
-    if (ablate & kAblWaves6) return 6;
     if (n_u <= 8) return kWavesU8;
     if (n_u <= 12) return (ablate & kAblWaves8) ? 8 : kWavesU12;
     return 6;
@@ -1100,6 +1099,32 @@ int tick_waves(int n_u, uint32_t ablate) {
 // non-temporal run 160 us; profiles/r07a_ntab.txt).  Not the lane-group recipient stores
 // (kNtFanGroupStore: config[3] 377 vs 415 us, config[4] 94 vs 107 us; profiles/r08i_*)
 constexpr uint32_t kJitNtDefault = kNtSchedLoad | kNtFanStore;
+
+// What the hipRTC build of a world's k_tick is made with, from the environment and the world (d: its
+// Dev once committed; nfk_jit_preview's has no record ops and no NFGPU_ABLATE).
+struct JitOptions {
+    int waves;    // waves per SIMD of the register budget
+    uint32_t nt;  // non-temporal hints (kNt* bits of nfgpu_tick.hpp)
+    bool lb;      // the rank workgroups' code compiled in
+};
+JitOptions jit_options(const Dev& d) {
+    JitOptions o;
+    // The specialised kernel gets the register budget of 5 waves per SIMD (round 4: no spills, and
+    // the fan-out's LDS window grows with the budget): config[1] 82.7-83.7 vs 83.7-84.1 us at 6
+    // (12 VGPRs spilled), 97 at 7, 122 at 8; config[3] 342-344 vs 347-348 us
+    // (profiles/r11j_jit_waves_ab.txt; round 2's r02t_ab_waves.txt chose 6 over 7).
+    o.waves = (d.ablate & kAblWaves8) ? tick_waves(d.n_u, d.ablate) : kWavesJit;
+    if (const char* ew = getenv("NFGPU_JIT_WAVES")) o.waves = std::max(1, std::min(8, atoi(ew)));
+    // NFGPU_JIT_NT overrides the default hints
+    o.nt = kJitNtDefault;
+    if (const char* en = getenv("NFGPU_JIT_NT")) o.nt = (uint32_t)strtoul(en, nullptr, 0);
+    // a world whose frames never rank in k_tick (record ops: their counts come from k_records too; dense
+    // ranks by k_scan_tiles asked for with kAblScanKernel) has that code compiled out of its
+    // specialisation (NFGPU_JIT_LB=0 / 1 overrides, for A/B; Dev::lb_rank is decided per frame)
+    o.lb = !d.has_recops && !(d.ablate & kAblScanKernel);
+    if (const char* el = getenv("NFGPU_JIT_LB")) o.lb = el[0] == '1';
+    return o;
+}
 
 // Specialised k_tick kernels built in this process, by (device, variant, policy source): a
 // schema compiles once however many worlds use it.
@@ -1119,23 +1144,10 @@ void build_jit(World* w) {
         return;
     }
     const int u = std::max(w->d.n_u, 1);
-    // The specialised kernel gets the register budget of 5 waves per SIMD (round 4: no spills, and
-    // the fan-out's LDS window grows with the budget): config[1] 82.7-83.7 vs 83.7-84.1 us at 6
-    // (12 VGPRs spilled), 97 at 7, 122 at 8; config[3] 342-344 vs 347-348 us
-    // (profiles/r11j_jit_waves_ab.txt; round 2's r02t_ab_waves.txt chose 6 over 7).
-    int waves = (w->d.ablate & (kAblWaves6 | kAblWaves8 | kAblWaves5)) ? tick_waves(w->d.n_u, w->d.ablate) : kWavesJit;
-    if (const char* ew = getenv("NFGPU_JIT_WAVES")) waves = std::max(1, std::min(8, atoi(ew)));
-    const char* es = getenv("NFGPU_JIT_SPEC");
-    const bool spec = es && es[0] == '1';  // every program operand loaded with the schedule records
-    // non-temporal hints (kNt* bits of nfgpu_tick.hpp); NFGPU_JIT_NT overrides the default
-    uint32_t nt = kJitNtDefault;
-    if (const char* en = getenv("NFGPU_JIT_NT")) nt = (uint32_t)strtoul(en, nullptr, 0);
-    // a world whose frames never rank in k_tick (record ops: their counts come from k_records too; dense
-    // ranks by k_scan_tiles asked for with kAblScanKernel) has that code compiled out of its
-    // specialisation (NFGPU_JIT_LB=0 / 1 overrides, for A/B; Dev::lb_rank is decided per frame)
-    bool lb = !w->d.has_recops && !(w->d.ablate & kAblScanKernel);
-    if (const char* el = getenv("NFGPU_JIT_LB")) lb = el[0] == '1';
-    const std::string src = jit_schema_source(w->tab, w->d, spec, nt, lb);
+    const JitOptions jo = jit_options(w->d);
+    const int waves = jo.waves;
+    const bool lb = jo.lb;
+    const std::string src = jit_schema_source(w->tab, w->d, jo.nt, lb);
     int dev = 0;
     (void)hipGetDevice(&dev);
     const std::string key = std::to_string(dev) + "|" + std::to_string(waves) + "|" + std::to_string(u) + "|" + src;
@@ -2047,102 +2059,12 @@ int nfk_commit(void* world) {
     if (w->n_dst_union > NFK_MAX_TOUCH)
         return fail(NFK_ERR_TOUCH, "programs write more than NFK_MAX_TOUCH distinct properties");
 
-    // property columns (Tables::p_off / p_str): one plain column per property.  Two interleaved
-    // layouts are kept as timing variants (NFGPU_ABLATE): kAblGroupColumns, the properties one
-    // heartbeat program touches interleaved (one line per entity for a sparse kind), and
-    // kAblSigGroups, properties with the same access signature interleaved.  Plain columns measured
-    // fastest on config[1] (profiles/r01zo_ablate.log: 99.8 us vs 110.7 grouped, 104.8 by
-    // signature): a dense kind's strided 8-byte accesses cost twice the L2 requests per load and
-    // its write-backs cover half lines, while a sparse kind's extra lines are few.
-    std::vector<std::vector<int>> pgroups;
-    const char* ab_env = getenv("NFGPU_ABLATE");
-    const uint32_t ab_layout = ab_env ? (uint32_t)strtoul(ab_env, nullptr, 0) : 0u;
-    if (!(ab_layout & kAblGroupColumns)) {
-        // plain columns, or groups of properties with the same access signature (the set of
-        // (kind, read / write) that touch them): every access covers a group
-        const int NP = w->n_if;
-        std::vector<std::vector<int>> sig(NP);
-        for (int k = 0; k < NK && (ab_layout & kAblSigGroups); k++)
-            for (int i = 0; i < w->tab.nops[k]; i++) {
-                const nfk_op& op = w->tab.ops[k][i];
-                auto add = [&](int p, int rw) { if (p >= 0 && p < NP) sig[p].push_back(2 * k + rw); };
-                if (op.code == NFK_OP_IADD_CLAMP) {
-                    add(op.dst, 1);
-                    if (op.flags & NFK_A_PROP) add((int)op.a, 0);
-                    if (op.flags & NFK_LO_PROP) add((int)op.b, 0);
-                    if (op.flags & NFK_HI_PROP) add((int)op.c, 0);
-                } else if (op.code == NFK_OP_FLERP) {
-                    add(op.dst, 1);
-                    add((int)op.a, 0);
-                } else if (op.code == NFK_OP_FAFFINE) {
-                    add(op.dst, 1);
-                } else if (op.code == NFK_OP_ISET || op.code == NFK_OP_FSET) {
-                    add(op.dst, 1);
-                    if (op.flags & NFK_A_PROP) add((int)op.a, 0);
-                }
-                if ((op.flags & NFK_GUARD) && !(op.flags & NFK_GUARD_CELL)) add((int)(op.guard & 0xFFFF), 0);
-                if ((op.flags & NFK_GUARD) && (op.guard & NFK_GUARD_PROP)) add((int)(op.guard >> 19), 0);
-            }
-        std::map<std::vector<int>, int> gi;
-        for (int p = 0; p < NP; p++) {
-            auto& g = sig[p];
-            std::sort(g.begin(), g.end());
-            g.erase(std::unique(g.begin(), g.end()), g.end());
-            auto it = g.empty() ? gi.end() : gi.find(g);
-            if (it != gi.end() && pgroups[it->second].size() < 8) {
-                pgroups[it->second].push_back(p);
-            } else {
-                if (!g.empty()) gi[g] = (int)pgroups.size();
-                pgroups.push_back({p});
-            }
-        }
-    } else {
-        const int NP = w->n_if;
-        constexpr int kGroupMax = 8;
-        std::vector<int> par(NP), sz(NP, 1);
-        for (int p = 0; p < NP; p++) par[p] = p;
-        std::function<int(int)> find = [&](int x) { return par[x] == x ? x : par[x] = find(par[x]); };
-        // (NFGPU_GROUP_SKIP: a mask of kinds whose properties are not grouped, for A/B)
-        const uint32_t skip = getenv("NFGPU_GROUP_SKIP") ? (uint32_t)strtoul(getenv("NFGPU_GROUP_SKIP"), nullptr, 0) : 0u;
-        for (int k = 0; k < NK; k++) {
-            std::vector<int> ps;
-            for (int i = 0; i < w->tab.nops[k] && !((skip >> k) & 1); i++) {
-                const nfk_op& op = w->tab.ops[k][i];
-                if (op.code == NFK_OP_IADD_CLAMP) {
-                    ps.push_back(op.dst);
-                    if (op.flags & NFK_A_PROP) ps.push_back((int)op.a);
-                    if (op.flags & NFK_LO_PROP) ps.push_back((int)op.b);
-                    if (op.flags & NFK_HI_PROP) ps.push_back((int)op.c);
-                } else if (op.code == NFK_OP_FLERP) {
-                    ps.push_back(op.dst);
-                    ps.push_back((int)op.a);
-                } else if (op.code == NFK_OP_FAFFINE) {
-                    ps.push_back(op.dst);
-                } else if (op.code == NFK_OP_ISET || op.code == NFK_OP_FSET) {
-                    ps.push_back(op.dst);
-                    if (op.flags & NFK_A_PROP) ps.push_back((int)op.a);
-                }
-                if ((op.flags & NFK_GUARD) && !(op.flags & NFK_GUARD_CELL)) ps.push_back((int)(op.guard & 0xFFFF));
-                if ((op.flags & NFK_GUARD) && (op.guard & NFK_GUARD_PROP)) ps.push_back((int)(op.guard >> 19));
-            }
-            for (size_t i = 1; i < ps.size(); i++) {
-                const int a = find(ps[0]), b = find(ps[i]);
-                if (a != b && sz[a] + sz[b] <= kGroupMax) {
-                    par[b] = a;
-                    sz[a] += sz[b];
-                }
-            }
-        }
-        std::vector<int> gi(NP, -1);
-        for (int p = 0; p < NP; p++) {
-            const int r = find(p);
-            if (gi[r] < 0) {
-                gi[r] = (int)pgroups.size();
-                pgroups.emplace_back();
-            }
-            pgroups[gi[r]].push_back(p);
-        }
-    }
+    // property columns (Tables::p_off / p_str): one plain column per int / float property, laid out
+    // below.  Interleaved layouts (the properties one heartbeat program touches, or those with the
+    // same access signature, stored together) measured slower on config[1]
+    // (profiles/r01zo_ablate.log: 99.8 us vs 110.7 grouped, 104.8 by signature; again in
+    // r14f_sparse_groups_ab.txt): a dense kind's strided 8-byte accesses cost twice the L2 requests
+    // per load and its write-backs cover half lines, while a sparse kind's extra lines are few.
 
     // membership layout: scene-group segments, NFGUID order inside (see plan_membership)
     const int64_t n_slots = plan_segments(w, w->slack, w->segs);
@@ -2189,17 +2111,19 @@ int nfk_commit(void* world) {
     ALLOC(w->tab_d, sizeof(Tables));
     ALLOC(d.tally, (size_t)3 * kTallyN * 8 * 8);
     ALLOC(w->ctrl, sizeof(Ctrl));
-    const int64_t cpad = (ab_layout & kAblNoPad) ? 0 : kColPad / 8;  // column pad in values
-    d.s_kstr = cap + (int32_t)((ab_layout & kAblNoPad) ? 0 : kColPad / (int64_t)sizeof(SchedHot));
+    {
+        const char* ab = getenv("NFGPU_ABLATE");
+        d.ablate = ab ? (uint32_t)strtoul(ab, nullptr, 0) : 0u;
+    }
+    const int64_t cpad = kColPad / 8;  // column pad in values
+    d.s_kstr = cap + (int32_t)(kColPad / (int64_t)sizeof(SchedHot));
     ALLOC(d.pmem, ((size_t)cap + cpad) * (size_t)std::max(w->n_pw, 1) * 8);
     {
         int64_t off = 0;
-        for (const auto& g : pgroups) {
-            for (size_t i = 0; i < g.size(); i++) {
-                w->tab.p_off[g[i]] = off + (int64_t)i;
-                w->tab.p_str[g[i]] = (int32_t)g.size();
-            }
-            off += (int64_t)g.size() * cap + cpad;
+        for (int p = 0; p < w->n_if; p++) {
+            w->tab.p_off[p] = off;
+            w->tab.p_str[p] = 1;
+            off += (int64_t)cap + cpad;
         }
         // an object property is one 16-byte column: (data, head) of slot e at p_off + 2e
         for (int p = w->n_if; p < w->n_prop; p++) {
@@ -2225,10 +2149,6 @@ int nfk_commit(void* world) {
     ALLOC(w->slot_obj_d, (size_t)cap * 4);
     ALLOC(w->fan_desc_w, (size_t)cap * 8);
     d.fan_desc = w->fan_desc_w;
-    {
-        const char* ab = getenv("NFGPU_ABLATE");
-        d.ablate = ab ? (uint32_t)strtoul(ab, nullptr, 0) : 0u;
-    }
     d.pl_slot = w->pl_slot_w;
     // output staging sized for every tile of the slot capacity
     d.ev_tcap = kTile * std::max(w->n_dst_union, 1);  // grows for frames with standalone SetProperty groups
@@ -2294,14 +2214,12 @@ int nfk_commit(void* world) {
     HIPCHK(hipMemcpy(w->tab_d, &w->tab, sizeof(Tables), hipMemcpyHostToDevice));
     HIPCHK(hipMemset(w->ctrl, 0, sizeof(Ctrl)));
     HIPCHK(hipMemset(d.tally, 0, (size_t)3 * kTallyN * 8 * 8));
-    for (const auto& g : pgroups) {
-        const size_t gs = g.size();
-        std::vector<uint64_t> blk((size_t)cap * gs, 0);
-        for (size_t i = 0; i < gs; i++)
-            if (!w->init_props[g[i]].empty())
-                for (int32_t s = 0; s < d.N; s++)
-                    if (w->obj_of_slot[s] >= 0) blk[(size_t)s * gs + i] = w->init_props[g[i]][w->obj_of_slot[s]];
-        HIPCHK(hipMemcpy(d.pmem + w->tab.p_off[g[0]], blk.data(), blk.size() * 8, hipMemcpyHostToDevice));
+    for (int p = 0; p < w->n_if; p++) {
+        std::vector<uint64_t> blk((size_t)cap, 0);
+        if (!w->init_props[p].empty())
+            for (int32_t s = 0; s < d.N; s++)
+                if (w->obj_of_slot[s] >= 0) blk[(size_t)s] = w->init_props[p][w->obj_of_slot[s]];
+        HIPCHK(hipMemcpy(d.pmem + w->tab.p_off[p], blk.data(), blk.size() * 8, hipMemcpyHostToDevice));
     }
     for (int p = w->n_if; p < w->n_prop; p++) {
         std::vector<uint64_t> blk((size_t)cap * 2, 0);
@@ -4045,11 +3963,8 @@ static int execute_frame(World* w, int64_t now_ms, bool calls_only) {
             lds = std::max(lds, (size_t)(163840 / waves - 2560) & ~(size_t)1023);
         }
         d.lds_words = (int32_t)(lds / 4);
-        {  // XCD-contiguous tiles (Dev::xcd_map; NFGPU_TICK_XCD=0 deals them round-robin):
-           // config[3] 342 -> 331 us, config[1] unchanged (profiles/r11o_ktick_xcd_map_ab.txt)
-            static const int xm = getenv("NFGPU_TICK_XCD") ? atoi(getenv("NFGPU_TICK_XCD")) : 1;
-            d.xcd_map = xm;
-        }
+        // (k_tick deals its tiles XCD-contiguous, xcd_tile: config[3] 342 -> 331 us against round-robin,
+        // config[1] unchanged, profiles/r11o_ktick_xcd_map_ab.txt)
         // the variant whose register slots hold the frame's working set (no spills at 6 or more
         // waves per SIMD): this schema's own k_tick, else a generic instantiation
         // (... and the rank workgroups after the tiles': Dev::lb_rank)
@@ -4059,15 +3974,15 @@ static int execute_frame(World* w, int64_t now_ms, bool calls_only) {
             HIPCHK(hipModuleLaunchKernel(w->jit_fn, g.x, 1, 1, kTPB, 1, 1, (unsigned)lds, w->stream,
                                          args, nullptr));
         } else if (use_u && cells) {  // the library's instantiations with the guard-cell loads and replay
-            if (d.n_u <= 8 && !(d.ablate & kAblWaves6))
+            if (d.n_u <= 8)
                 hipLaunchKernelGGL((k_tick<kWavesU8, 8, DynSchemaCells>), g, b, lds, w->stream, d);
-            else if (d.n_u <= 12 && !(d.ablate & kAblWaves6))
+            else if (d.n_u <= 12)
                 hipLaunchKernelGGL((k_tick<kWavesU12, 12, DynSchemaCells>), g, b, lds, w->stream, d);
             else
                 hipLaunchKernelGGL((k_tick<6, 16, DynSchemaCells>), g, b, lds, w->stream, d);
-        } else if (use_u && d.n_u <= 8 && !(d.ablate & kAblWaves6))
+        } else if (use_u && d.n_u <= 8)
             hipLaunchKernelGGL((k_tick<kWavesU8, 8>), g, b, lds, w->stream, d);
-        else if (use_u && d.n_u <= 12 && !(d.ablate & kAblWaves6))
+        else if (use_u && d.n_u <= 12)
             hipLaunchKernelGGL((k_tick<kWavesU12, 12>), g, b, lds, w->stream, d);
         else if (use_u)
             hipLaunchKernelGGL((k_tick<6, 16>), g, b, lds, w->stream, d);
@@ -4129,7 +4044,7 @@ static int execute_frame(World* w, int64_t now_ms, bool calls_only) {
     w->scan_pending = false;
     if (d.lb_rank) {
         // (written by k_tick's rank workgroups)
-    } else if (d.fuse_fan && (!d.has_recops || d.fuse_rec) && !(d.ablate & kAblScanInFrame)) {
+    } else if (d.fuse_fan && (!d.has_recops || d.fuse_rec)) {
         w->scan_pending = true;
         w->scan_dev = d;
     } else {
@@ -4946,19 +4861,15 @@ int nfk_jit_preview_rec(int32_t n_int, int32_t n_flt, int32_t n_class, int32_t n
         copy_msg("working set does not fit k_tick (k_tick_touch runs)", msg, msg_cap);
         return NFK_OK;
     }
-    const char* es = getenv("NFGPU_JIT_SPEC");
-    uint32_t nt = kJitNtDefault;
-    if (const char* en = getenv("NFGPU_JIT_NT")) nt = (uint32_t)strtoul(en, nullptr, 0);
-    bool lb = true;  // (rank workgroups compiled in, as for a world without record ops; NFGPU_JIT_LB as at commit)
-    if (const char* el = getenv("NFGPU_JIT_LB")) lb = el[0] == '1';
-    const std::string s = jit_schema_source(*tab, d, es && es[0] == '1', nt, lb);
+    const JitOptions jo = jit_options(d);  // (rank workgroups compiled in, as for a world without record ops)
+    const std::string s = jit_schema_source(*tab, d, jo.nt, jo.lb);
     copy_msg(s, src, src_cap);
     if (!compile) {
         *ok = 1;
         return NFK_OK;
     }
-    const int u = std::max(d.n_u, 1), waves = kWavesJit;
-    JitBuild b = jit_compile(s, waves, u, true);  // (with the kernels' resource usage in the log)
+    const int u = std::max(d.n_u, 1);
+    JitBuild b = jit_compile(s, jo.waves, u, true);  // (with the kernels' resource usage in the log)
     *ok = b.ok;
     if (b.ok) {
         // the compiler's log as before (its warnings), then the kernels' resource remarks, each cut to

@@ -1605,7 +1605,7 @@ __global__ __launch_bounds__(kScanTPB) void k_scan_tiles(Dev d) {
 // per tile (property tiles, then record tiles; blockIdx.x + blk0 is the tile).  When k_tick
 // writes its own tiles' fan-out this runs for the record tiles only.  Each tile's messages are
 // one contiguous run at msg_base[tile] (k_scan_tiles).  A pass takes up to kTPB * kFanPer
-// events: their (first message, first player | slot, count | rank | public) triples go to LDS,
+// events: their (first message, first player | slot, count | rank | public) triples (FanEv) go to LDS,
 // and each event is then expanded by a group of L lanes (L = the pass's largest recipient count
 // rounded up to a power of two, at most 64), so a group of 32 players fills half a wave per event
 // and a 2-player group an eighth.  Slots are in (scene, group, guid) order, so the players of
@@ -1695,10 +1695,7 @@ __global__ __launch_bounds__(kTPB) void k_fanout(Dev d, int32_t blk0) {
                 const uint32_t n = event_msgs(desc, fl);
                 const bool pub = fl & NFK_PUBLIC;
                 const uint32_t src = (uint32_t)desc, np = (uint32_t)((desc >> 32) & 0x3FFF);
-                uint32_t* x = s_ev + 3 * (i - c0);
-                x[0] = lm[q];
-                x[1] = pub ? src : slot[q];
-                x[2] = n | ((uint32_t)((desc >> 46) & 0x3FFF) << 14) | (pub ? 0x80000000u : 0u);
+                fan_ev_put(s_ev + 3 * (i - c0), lm[q], pub ? src : slot[q], n, (uint32_t)((desc >> 46) & 0x3FFF), pub);
                 moff[off0 + i] = mbase + lm[q];
                 bytes += 4 + 4 + 4 + 8 + 4 + 4 * n;
                 nmax = max(nmax, n);
@@ -1710,18 +1707,13 @@ __global__ __launch_bounds__(kTPB) void k_fanout(Dev d, int32_t blk0) {
             if (i == c0) s_m[0] = lm[q];
         }
         if (threadIdx.x == 0) s_m[1] = c_end < cnt ? moff[off0 + c_end] : tmsg;
-#pragma unroll
-        for (int m = 32; m >= 1; m >>= 1) {
-            lo = min(lo, (uint32_t)__shfl_xor((int)lo, m, 64));
-            hi = max(hi, (uint32_t)__shfl_xor((int)hi, m, 64));
-            nmax = max(nmax, (uint32_t)__shfl_xor((int)nmax, m, 64));
-        }
+        fan_run_reduce(lo, hi, nmax);
         if (lane == 0) {
             if (hi) {
                 atomicMin(&s_pb[0], lo);
                 atomicMax(&s_pb[1], hi);
             }
-            atomicMax(&s_pb[2], nmax);
+            atomicMax(&s_pb[2], nmax);  // (a wave of private events only has no run, but a count)
         }
         __syncthreads();
         const uint32_t p0 = s_m[0], pn = s_m[1] - s_m[0];
@@ -1739,14 +1731,14 @@ __global__ __launch_bounds__(kTPB) void k_fanout(Dev d, int32_t blk0) {
         uint32_t* out = lds_out ? s_msg : d.msg_rcpt + mbase + p0;
         const uint32_t sub = threadIdx.x & (L - 1);
         for (uint32_t i = threadIdx.x / L; i < c_end - c0; i += kTPB / L) {
-            const uint32_t ms = s_ev[3 * i] - p0, a = s_ev[3 * i + 1], b = s_ev[3 * i + 2];
-            const uint32_t n = b & 0x3FFFu, r1 = (b >> 14) & 0x3FFFu;
-            if (!(b >> 31)) {  // private & !upload: the entity itself (n is 0 or 1)
-                if (sub < n) out[ms] = a;
+            const FanEv ev = fan_ev_get(s_ev + 3 * i);
+            const uint32_t ms = ev.ms - p0, a = ev.a;  // (message starts are the tile's: the pass's begin at p0)
+            if (!ev.pub) {  // private & !upload: the entity itself (n is 0 or 1)
+                if (sub < ev.n) out[ms] = a;
                 continue;
             }
-            for (uint32_t p = sub; p < n; p += L) {  // every player of the group but self
-                const uint32_t pp = p + ((r1 && p + 1 >= r1) ? 1u : 0u);
+            for (uint32_t p = sub; p < ev.n; p += L) {  // every player of the group but self
+                const uint32_t pp = skip_self(p, ev.r1);
                 out[ms + p] = staged ? s_pl[a - pb_lo + pp] : (uint32_t)d.pl_slot[a + pp];
             }
         }
@@ -1754,9 +1746,7 @@ __global__ __launch_bounds__(kTPB) void k_fanout(Dev d, int32_t blk0) {
             __syncthreads();
             uint32_t* dst = d.msg_rcpt + mbase + p0;
             if (((mbase + p0) & 3u) == 0) {
-                const uint32_t n4 = pn >> 2;
-                for (uint32_t i = threadIdx.x; i < n4; i += kTPB) ((uint4*)dst)[i] = ((const uint4*)s_msg)[i];
-                if (threadIdx.x < (pn & 3u)) dst[4 * n4 + threadIdx.x] = s_msg[4 * n4 + threadIdx.x];
+                lds_flush16<false>(dst, s_msg, pn);
             } else {
                 for (uint32_t i = threadIdx.x; i < pn; i += kTPB) dst[i] = s_msg[i];
             }

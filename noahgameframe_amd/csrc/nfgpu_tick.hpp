@@ -194,7 +194,6 @@ template <bool kCells>
 struct DynSchemaT {
     static constexpr bool kStatic = false;
     static constexpr bool kOff32 = false;  // 64-bit element addresses (any world size)
-    static constexpr uint32_t kSpecMask = 0;  // operands loaded before the fire test (none)
     // non-temporal hints (kNt* bits): none in the library's instantiations
     static constexpr uint32_t kNt = 0;
     // k_tick may rank the frame's tiles itself (Dev::lb_rank: the tiles publish their counts, rank
@@ -498,6 +497,47 @@ __device__ void lb_rank_wg(const Dev& d, const int q, unsigned long long* s_w, u
     }
 }
 
+// ---- fan-out pieces shared by k_tick's tail and k_fanout (nfgpu_kernels.hip) ----
+// An event of a fan-out chunk in LDS, three words: its first message; the first player of its
+// group's pl_slot run (a public event) or the entity's own slot (a private one); and
+// count | r1 << 14 | public << 31, r1 = 1 + the entity's rank among its group's players (0: not one).
+struct FanEv {
+    uint32_t ms, a, n, r1;
+    bool pub;
+};
+__device__ __forceinline__ void fan_ev_put(uint32_t* x, uint32_t ms, uint32_t a, uint32_t n, uint32_t r1, bool pub) {
+    x[0] = ms;
+    x[1] = a;
+    x[2] = n | (r1 << 14) | (pub ? 0x80000000u : 0u);
+}
+__device__ __forceinline__ FanEv fan_ev_get(const uint32_t* x) {
+    const uint32_t b = x[2];
+    return FanEv{x[0], x[1], b & 0x3FFFu, (b >> 14) & 0x3FFFu, (b >> 31) != 0};
+}
+// every player of the group but self: recipient p of an entity that is the group's r1-th player
+// (r1 = 0: not a player) is player skip_self(p, r1) of the group's run
+__device__ __forceinline__ uint32_t skip_self(uint32_t p, uint32_t r1) { return p + ((r1 && p + 1 >= r1) ? 1u : 0u); }
+// A thread's part of the pl_slot run [lo, hi) of the groups with messages (hi = 0: none) and its
+// largest recipient count, reduced over the wave.  Merging them into s_pb is the caller's: k_tick
+// raises the largest count for a wave with a run, k_fanout for every wave.
+__device__ __forceinline__ void fan_run_reduce(uint32_t& lo, uint32_t& hi, uint32_t& nmax) {
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) {
+        lo = min(lo, (uint32_t)__shfl_xor((int)lo, m, 64));
+        hi = max(hi, (uint32_t)__shfl_xor((int)hi, m, 64));
+        nmax = max(nmax, (uint32_t)__shfl_xor((int)nmax, m, 64));
+    }
+}
+// n words of LDS to a 16-byte aligned run of global memory: 16-byte stores and a tail of up to 3 words
+template <bool NT>
+__device__ __forceinline__ void lds_flush16(uint32_t* dst, const uint32_t* src, uint32_t n) {
+    const uint32_t n4 = n >> 2;
+    uint4* dst4 = (uint4*)dst;
+    const uint4* src4 = (const uint4*)src;
+    for (uint32_t i = threadIdx.x; i < n4; i += kTPB) st_nt<NT>(dst4 + i, src4[i]);
+    if (threadIdx.x < (n & 3u)) dst[4 * n4 + threadIdx.x] = src[4 * n4 + threadIdx.x];
+}
+
 // k_tick: one thread per slot, one workgroup per 256-slot tile, on the programs' working set
 // (Dev::u_*, fixed at commit).  Every value the entity's frame touches is loaded in ONE batch of
 // independent loads into registers; the fired kinds' programs run on those registers with
@@ -509,26 +549,550 @@ __device__ void lb_rank_wg(const Dev& d, const int q, unsigned long long* s_w, u
 // k_scan_tiles, or this kernel's rank workgroups (Dev::lb_rank), turn the counts into global ranks.
 // kWPE: waves per SIMD the register allocation aims at.  The LDS image of the frame-start values
 // is dynamic: n_w writable slots x kTPB.
-// Dev::xcd_map: workgroup b (dealt to XCD b mod 8) -> a tile of that XCD's contiguous range
+// Workgroup b (dealt to XCD b mod 8) runs a tile of that XCD's contiguous range: the workgroups of
+// one XCD take neighbouring tiles, which its L2 holds (profiles/r11o_ktick_xcd_map_ab.txt)
 __device__ __forceinline__ int xcd_tile(int b, int n) {
     const int x = b & 7, i = b >> 3, q = n >> 3, r = n & 7;
     return x * q + min(x, r) + i;
+}
+
+// A thread's state of its tile's frame, handed from phase to phase of tick_tile (the working set's
+// registers v[kU] travel beside it).
+struct TickSt {
+    int e;                 // the thread's slot
+    uint64_t desc;         // its fan-out descriptor (kDeadDesc past N and for a slack slot)
+    uint32_t fired;        // kinds that fired
+    uint32_t xh;           // 1 + the slot's first queued Set group (0: none)
+    uint32_t xset;         // writable slots that are destinations of a queued Set
+    uint32_t wm, dm;       // slots a Set changed at least once (bits 16+: used guard cells); dirty slots
+    uint32_t pubm, privm;  // the class's public / private-only writable slots (Dev::u_cmask)
+    uint32_t npub, r1;     // recipients of a public event; 1 + rank among the group's players (0: not one)
+    unsigned nsd;          // standalone Set events
+    unsigned nd, nmsg;     // events and messages
+    unsigned nmax;         // largest recipient count of one event
+    unsigned pev0, pfi, pmsg0;  // the block scan's prefixes: first event, fired heartbeat, message in the tile
+    unsigned bytes;        // algorithmic bytes (the tally)
+};
+
+// (block-uniform) a calls-only pass and no Set group in this tile: nothing fires, nothing is dirty
+template <class S>
+__device__ __forceinline__ void tick_idle_tile(const Dev& d, const int tile, const int e) {
+    if (d.has_recops && e < d.N) d.fired_mask[e] = 0;
+    if (threadIdx.x == 0) {
+        d.t_ev[tile] = 0;
+        d.t_fi[tile] = 0;
+        d.t_msg[tile] = 0;
+    }
+    if (S::kLb && d.lb_rank) lb_publish(d, tile, 0u, 0u, 0u);
+}
+
+// Load and run: the schedule scan, the slot's queued Set groups, one batch of operand and cell loads,
+// the frame-start image (s_o), the fired kinds' programs, the dirty diff, and the write-back of the
+// Sets a program undid.
+template <int kU, class S>
+__device__ __forceinline__ void tick_load_run(const Dev& d, TickSt& t, uint64_t (&v)[kU], uint64_t* s_o, int32_t* s_rem) {
+    constexpr int kW = kU < kMaxW ? kU : kMaxW;  // writable register slots
+    const int e = t.e;
+    {
+        // descriptor and schedule records in one round trip, without a branch: slots past N (the
+        // last tile) re-read slot N-1 and count as dead; a dead slot stores nothing
+        const int ec = e < d.N ? e : d.N - 1;
+        t.fired = sched_scan<S>(d, ec, t.bytes, t.desc, s_rem, e >= d.N);  // NFCScheduleModule::Execute (SM:51-81)
+        t.desc = e < d.N ? t.desc : kDeadDesc;
+        t.bytes = e < d.N ? t.bytes + 8 : 0u;
+    }
+    const bool live = !desc_dead(t.desc);
+    // queued Set groups of this slot (k_sets ran them): program destinations among them
+    // (queued Sets are the rare case, here and below: most frames have none, and few entities of a
+    // frame that has; the hints keep that code off the programs' path, which the library's 8- and
+    // 16-slot instantiations pay for in spills otherwise: profiles/r20a_tick_phases.txt)
+    if (live && __builtin_expect(d.n_x != 0, 0)) {
+        t.xh = *elem<S>(d.ext_head, (uint32_t)e);
+        t.bytes += 4;
+        if (t.xh)
+            for (int g = (int)t.xh - 1; g < d.n_x && d.x_slot[g] == (uint32_t)e; g++) {
+                const uint32_t j = d.tab->w_slot[d.x_pid[g]];
+                t.xset |= j != kNoU ? 1u << j : 0u;
+                t.bytes += 8;
+            }
+    }
+    uint32_t need = 0, cu = 0;  // cu: the guard-cell slots whose row is used
+    if (live) {
+        need = t.xset;
+        if (!(d.ablate & kAblPrograms)) need |= S::need(d, t.fired);
+        // one batch of independent loads: every value this entity's frame reads or writes
+#pragma unroll
+        for (int j = 0; j < kU; j++)
+            if (((need >> j) & 1) && !slot_is_cell<S>(d, j) && !(d.ablate & kAblNoLoads)) {
+                v[j] = ld_nt<(S::kNt & kNtColLoad) != 0>(elem<S>(d.u_col[j], (uint32_t)e, S::u_str(d, j)));
+                t.bytes += 8;
+            }
+        if (!(d.ablate & kAblNoLoads)) cu = cell_loads<kU, S>(d, e, need, v, t.bytes);
+    }
+    if (live) {
+#pragma unroll
+        for (int j = 0; j < kW; j++)
+            if (j < S::n_w(d) && ((need >> j) & 1)) s_o[j * kTPB + threadIdx.x] = v[j];
+        // a Set program destination: its frame-start value is the value before the Set group
+        if (t.xset) {
+            for (int g = (int)t.xh - 1; g < d.n_x && d.x_slot[g] == (uint32_t)e; g++) {
+                const uint32_t j = d.tab->w_slot[d.x_pid[g]];
+                if (j != kNoU) s_o[j * kTPB + threadIdx.x] = d.x_old[g];
+                t.bytes += j != kNoU ? 8 : 0;
+            }
+            t.wm = t.xset;
+        }
+        // the fired heartbeats' effect programs, in schedule-name order
+        t.wm |= cu << 16;  // (run_programs_u: the used guard cells take the walk's record ops)
+        if (!(d.ablate & (kAblPrograms | kAblNoRun)) && t.fired) S::run(v, t.wm, d, t.fired);
+    }
+    // dirty diff against the frame-start values
+#pragma unroll
+    for (int j = 0; j < kW; j++)
+        if (((t.wm >> j) & 1) && v[j] != s_o[j * kTPB + threadIdx.x]) t.dm |= 1u << j;
+    // a Set program destination that a program moved back to its frame-start value has no event,
+    // but k_sets changed its column: write it back here (the dirty slots are written with their
+    // events)
+    if (__builtin_expect((t.xset & ~t.dm) != 0, 0))
+#pragma unroll
+        for (int j = 0; j < kW; j++)
+            if (j < S::n_w(d) && ((t.xset & ~t.dm) >> j) & 1) {
+                *elem<S>(d.u_col[j], (uint32_t)e, S::u_str(d, j)) = v[j];
+                t.bytes += 8;
+            }
+}
+
+// Counts.  Fan-out message counts (event_msgs): a public property's event goes to every player of the
+// group but the entity itself, a private & !upload one to the entity only.  The message offset
+// of a slot's event = the counts of the dirty slots with lower property ids (Dev::u_lower).
+template <class S>
+__device__ __forceinline__ void tick_counts(const Dev& d, TickSt& t) {
+    // the entity's class's event masks (Dev::u_cmask; class 15, a free slot: no slots): a select
+    // over kernel-argument scalars, no indexed copy and no barrier
+    const uint32_t cm = S::class_mask(d, (unsigned)(t.desc >> 60));
+    t.pubm = cm & 0xFFFFu;
+    t.privm = cm >> 16;
+    t.r1 = (uint32_t)((t.desc >> 46) & 0x3FFF);
+    t.npub = (uint32_t)((t.desc >> 32) & 0x3FFF) - (t.r1 ? 1u : 0u);
+    t.nmsg = t.npub * __builtin_popcount(t.dm & t.pubm) + __builtin_popcount(t.dm & t.privm);
+    t.nmax = (t.dm & t.pubm) ? t.npub : ((t.dm & t.privm) ? 1u : 0u);
+    t.nd = __builtin_popcount(t.dm);
+    // standalone Set events (properties no program writes): counted here, merged in property-id
+    // order with the slots' events by walk_events
+    if (t.xh) {
+        for (int g = next_standalone(d, (int)t.xh - 1, t.e); g < d.n_x; g = next_standalone(d, g + 1, t.e)) {
+            const EvFan f = ev_fan(d, t.desc, d.x_pid[g]);
+            t.nsd++;
+            t.nmsg += f.n;
+            t.nmax = max(t.nmax, f.n);
+            t.bytes += 8;
+        }
+        t.nd += t.nsd;
+    }
+}
+
+// the entity's events in property-id order: dirty slots (u_order) merged with the standalone
+// groups; emit(rank, message offset, pid, slot or -1, group, recipients) per event
+template <class S, class Emit>
+__device__ __forceinline__ void walk_events(const Dev& d, const TickSt& t, Emit&& emit) {
+    int g = next_standalone(d, (int)t.xh - 1, t.e);
+    unsigned at = 0, m = 0;
+#pragma unroll 1
+    for (int i = 0; i <= S::n_w(d); i++) {
+        const int j = i < S::n_w(d) ? S::u_order(d, i) : -1;
+        const uint32_t pj = j >= 0 ? (uint32_t)S::u_pid(d, j) : 0xFFFFFFFFu;
+        while (g < d.n_x && d.x_pid[g] < pj) {
+            const EvFan f = ev_fan(d, t.desc, d.x_pid[g]);
+            emit(at, m, d.x_pid[g], -1, g, f);
+            at++;
+            m += f.n;
+            g = next_standalone(d, g + 1, t.e);
+        }
+        if (j >= 0 && ((t.dm >> j) & 1)) {
+            const bool pub = (t.pubm >> j) & 1;
+            const EvFan f{pub ? t.npub : ((t.privm >> j) & 1u), pub};
+            emit(at, m, pj, j, 0, f);
+            at++;
+            m += f.n;
+        }
+    }
+}
+
+// Write back the changed values; their events in property-id order (rank among the entity's dirty
+// slots by Dev::u_lower) at the tile's output run ev0.  !fuse: the events' tile-local message offsets
+// too (k_fanout adds the tile's message base).
+template <int kU, class S>
+__device__ __forceinline__ void emit_events(const Dev& d, TickSt& t, const uint64_t (&v)[kU], const uint64_t* s_o,
+                                            const size_t ev0, const bool fuse) {
+    constexpr int kW = kU < kMaxW ? kU : kMaxW;
+    const int e = t.e;
+    const uint32_t dm = t.dm, pubm = t.pubm, privm = t.privm, npub = t.npub;
+    const unsigned pev0 = t.pev0, pmsg0 = t.pmsg0;
+    uint32_t* const t_evm = d.ev_moff + ev0;
+    uint32_t* const t_evs = d.ev_slot + ev0;
+    uint32_t* const t_evp = d.ev_pid + ev0;
+    uint64_t* const t_evo = d.ev_old + ev0;
+    uint64_t* const t_evn = d.ev_new + ev0;
+    if (!t.nsd) {
+        // A thread's events sit at consecutive ranks, so two consecutive ones are stored
+        // together (8-byte stores of the slot and pid words, 16-byte stores of the old and
+        // new values, at any dword): one store per array covers most of a wave's run instead
+        // of one per event slot with the lanes ~2.4 events apart
+        // (tools/event_store_probe.hip: 22.4 -> 18.8 us for config[1]'s 2.5M events)
+        constexpr bool kNE = (S::kNt & kNtEventStore) != 0;
+        bool pend = false;  // an event held back to be stored with the next one
+        uint32_t pa = 0, pp = 0;
+        uint64_t po = 0, pn = 0;
+#pragma unroll
+        for (int j = 0; j < kW; j++) {
+            if (j >= S::n_w(d) || !((dm >> j) & 1)) continue;
+            const uint32_t below = dm & S::u_lower(d, j);
+            const uint32_t at = pev0 + __builtin_popcount(below);
+            const uint64_t nv = v[j], ov = s_o[j * kTPB + threadIdx.x];
+            const uint32_t pid = (uint32_t)S::u_pid(d, j);
+            if (!(d.ablate & kAblNoWriteBack)) st_nt<(S::kNt & kNtStateStore) != 0>(elem<S>(d.u_col[j], (uint32_t)e, S::u_str(d, j)), nv);
+            if (!fuse)  // tile-local; k_fanout adds the tile's message base
+                st_off(t_evm, at, pmsg0 + npub * __builtin_popcount(below & pubm) +
+                                      __builtin_popcount(below & privm));
+            if (d.ablate & kAblNoEvStore) {
+            } else if (pend && at == pa + 1) {  // (the writable slots are in property-id order)
+                st_vec<kNE>(t_evs, 4u * pa, u32x2_a4{(uint32_t)e, (uint32_t)e});
+                st_vec<kNE>(t_evp, 4u * pa, u32x2_a4{pp, pid});
+                st_vec<kNE>(t_evo, 8u * pa, u32x4_a4{(uint32_t)po, (uint32_t)(po >> 32), (uint32_t)ov, (uint32_t)(ov >> 32)});
+                st_vec<kNE>(t_evn, 8u * pa, u32x4_a4{(uint32_t)pn, (uint32_t)(pn >> 32), (uint32_t)nv, (uint32_t)(nv >> 32)});
+                pend = false;
+            } else {
+                if (pend) {
+                    st_off_nt<kNE>(t_evs, pa, (uint32_t)e);
+                    st_off_nt<kNE>(t_evp, pa, pp);
+                    st_off_nt<kNE>(t_evo, pa, po);
+                    st_off_nt<kNE>(t_evn, pa, pn);
+                }
+                pend = true;
+                pa = at;
+                pp = pid;
+                po = ov;
+                pn = nv;
+            }
+            t.bytes += 8 + 24;
+        }
+        if (pend && !(d.ablate & kAblNoEvStore)) {
+            st_off_nt<kNE>(t_evs, pa, (uint32_t)e);
+            st_off_nt<kNE>(t_evp, pa, pp);
+            st_off_nt<kNE>(t_evo, pa, po);
+            st_off_nt<kNE>(t_evn, pa, pn);
+        }
+    } else {
+        // (rare: an entity with standalone Set events) write back the slots, then every
+        // event by the merged walk, which reads the slots' new values back from their
+        // columns so that no register of the working set stays live in it
+#pragma unroll
+        for (int j = 0; j < kW; j++)
+            if (j < S::n_w(d) && ((dm >> j) & 1)) {
+                *elem<S>(d.u_col[j], (uint32_t)e, S::u_str(d, j)) = v[j];
+                t.bytes += 8;
+            }
+        unsigned& bytes = t.bytes;
+        walk_events<S>(d, t, [&](unsigned at, unsigned m, uint32_t pid, int j, int g, EvFan) {
+            uint64_t ov, nv;
+            if (j >= 0) {
+                ov = s_o[j * kTPB + threadIdx.x];
+                nv = __hip_atomic_load(elem<S>(d.u_col[j], (uint32_t)e, S::u_str(d, j)), __ATOMIC_RELAXED,
+                                       __HIP_MEMORY_SCOPE_WAVEFRONT);
+            } else {  // (k_sets wrote the column)
+                ov = d.x_old[g];
+                nv = d.x_new[g];
+                if ((int)pid >= d.n_if) {  // an object property: its head halves beside
+                    st_off(d.ev_old_h + ev0, pev0 + at, d.x_old_h[g]);
+                    st_off(d.ev_new_h + ev0, pev0 + at, d.x_new_h[g]);
+                    bytes += 16;
+                }
+            }
+            st_off(t_evs, pev0 + at, (uint32_t)e);
+            st_off(t_evp, pev0 + at, pid);
+            st_off(t_evo, pev0 + at, ov);
+            st_off(t_evn, pev0 + at, nv);
+            if (!fuse) st_off(t_evm, pev0 + at, pmsg0 + m);
+            bytes += 24;
+        });
+    }
+}
+
+// the thread's fired heartbeats into the tile's fired list at fi0: (slot, kind, remain after the fire)
+template <class S>
+__device__ __forceinline__ void emit_fired(const Dev& d, TickSt& t, const int32_t* s_rem, const size_t fi0) {
+    const int e = t.e;
+    uint32_t* const t_fis = d.fi_slot + fi0;
+    uint32_t* const t_fik = d.fi_kind + fi0;
+    int32_t* const t_fir = d.fi_remain + fi0;
+    unsigned pfi = t.pfi;
+    uint32_t fl = t.fired;
+    while (fl) {
+        const int k = __builtin_ctz(fl);
+        fl &= fl - 1;
+        constexpr bool kNE = (S::kNt & kNtEventStore) != 0;
+        const int32_t rem = s_rem[k * kTPB + threadIdx.x];
+        // (a forever heartbeat's remain may be any int32, the sentinel too: sched_edges worlds
+        // wrap it through INT32_MIN; a counted one is >= 0 after a fire.  The forever bit is the
+        // same before and after the scan, so the record's state is read whatever the L1 holds)
+        if ((d.ablate & kAblCheckRem) && rem == kRemUnset &&
+            !(elem<S>(d.s_hot + (size_t)k * d.s_kstr, (uint32_t)e)->state & kStForever))
+            dev_error(d, kErrRemain);
+        if (!(d.ablate & kAblNoFiStore)) {
+            st_off_nt<kNE>(t_fis, pfi, (uint32_t)e);
+            st_off_nt<kNE>(t_fik, pfi, (uint32_t)k);
+            st_off_nt<kNE>(t_fir, pfi, rem);
+        }
+        pfi++;
+        t.bytes += 12;
+    }
+}
+
+// ---- k_tick's fan-out (GetBroadCastObject, AOI:531-593; see k_fanout) ----
+// A tile's recipients go into its fixed-stride run `out` (msg_rcpt + tile * msg_tcap) in event order.
+// The LDS region of the frame-start image (R words at s_o) is reused, in one of three forms that
+// fan_out chooses for the whole tile: fan_direct, or chunks of event triples (fan_fill) expanded by
+// fan_lane_groups or fan_window.
+// What the three forms share: the region's layout and the groups' player run.
+struct FanLds {
+    uint32_t* s_ev;    // a chunk's event triples (FanEv)
+    uint32_t* s_win;   // the message window behind them (fan_window)
+    uint32_t* s_pl;    // the staged player run at the region's end (staged)
+    uint32_t pb_lo;    // its first index in pl_slot
+    bool staged;       // else the players are read from pl_slot
+};
+// player p of the run that starts at pl_slot[a], from the staged run when there is one
+__device__ __forceinline__ uint32_t fan_player(const Dev& d, const FanLds& f, uint32_t a, uint32_t p) {
+    return f.staged ? f.s_pl[a - f.pb_lo + p] : (uint32_t)d.pl_slot[a + p];
+}
+
+// Short runs whose tile's whole run fits beside the staged players: no triples, no event loop and
+// no window passes.  A thread knows its own events and their message offsets, so it writes their
+// recipients straight into the window [0, tmsg) at s_run (tile-local offsets), and the window is
+// stored once.  The players are read from pl_slot through L1 (a group's run is read by its ~250
+// neighbouring threads), which saves the staging and its barrier.  nm: the tile's largest run.
+template <int kU, class S>
+__device__ __forceinline__ void fan_direct(const Dev& d, const TickSt& t, uint32_t* const s_run, uint32_t* out,
+                                           const unsigned tmsg, const uint32_t nm) {
+    constexpr int kW = kU < kMaxW ? kU : kMaxW;
+    const int e = t.e;
+    const uint64_t desc = t.desc;
+    const uint32_t dm = t.dm, pubm = t.pubm, privm = t.privm, npub = t.npub, r1 = t.r1;
+    const unsigned pmsg0 = t.pmsg0;
+    if (t.nsd) {  // (rare) the merged walk gives each event's offset and recipients
+        walk_events<S>(d, t, [&](unsigned, unsigned m, uint32_t, int, int, EvFan f) {
+            uint32_t* w = s_run + pmsg0 + m;
+            if (!f.pub) {
+                if (f.n) w[0] = (uint32_t)e;
+                return;
+            }
+            const auto* pl = d.pl_slot + (uint32_t)desc;
+            for (uint32_t k = 0; k < f.n; k++) w[k] = (uint32_t)pl[skip_self(k, r1)];
+        });
+    } else if (t.nmsg) {
+        // public events with recipients: the q-th one's run starts npub * q + (the
+        // private events before it: 4 bits each in pk) words after the thread's first
+        const uint32_t dpub = npub ? dm & pubm : 0u, dprv = dm & privm;
+        unsigned long long pk = 0;
+        if (dprv) {  // a private event goes to the entity itself
+#pragma unroll
+            for (int j = 0; j < kW; j++) {
+                if (j >= S::n_w(d)) continue;
+                const uint32_t below = dm & S::u_lower(d, j);
+                const uint32_t q = __builtin_popcount(below & pubm), pv = __builtin_popcount(below & privm);
+                if ((dprv >> j) & 1) s_run[pmsg0 + npub * q + pv] = (uint32_t)e;
+                pk |= ((dpub >> j) & 1) ? (unsigned long long)pv << (4u * q) : 0ull;
+            }
+        }
+        const uint32_t npe = __builtin_popcount(dpub);
+        if (npe) {
+            // eight recipients at a time, read once and written to every public event's
+            // run: a store past a run's end repeats its last word (the same value at the
+            // same place), so only the event loop's trip count differs between lanes
+            const auto* pl = d.pl_slot + (uint32_t)desc;
+#pragma unroll 1
+            for (uint32_t k0 = 0; k0 < nm; k0 += 8) {  // uniform
+                uint32_t x[8], o[8];
+#pragma unroll
+                for (int k = 0; k < 8; k++) {  // every player of the group but self
+                    o[k] = min(k0 + (uint32_t)k, npub - 1u);
+                    x[k] = (uint32_t)pl[skip_self(o[k], r1)];
+                }
+                uint32_t* w = s_run + pmsg0;
+                unsigned long long pq = pk;
+                for (uint32_t q = 0; q < npe; q++) {
+                    uint32_t* wq = w + ((uint32_t)pq & 15u);
+#pragma unroll
+                    for (int k = 0; k < 8; k++) wq[o[k]] = x[k];
+                    w += npub;
+                    pq >>= 4;
+                }
+            }
+        }
+    }
+    __syncthreads();
+    // out is 16-byte aligned (msg_tcap is a multiple of 4); nothing refills the window
+    lds_flush16<(S::kNt & kNtFanStore) != 0>(out, s_run, tmsg);
+}
+
+// The thread's events of the chunk [c0, c1) of the tile's events as triples at f.s_ev.
+template <class S>
+__device__ __forceinline__ void fan_fill(const Dev& d, const TickSt& t, const FanLds& f, const unsigned c0, const unsigned c1) {
+    const int e = t.e;
+    const uint64_t desc = t.desc;
+    const uint32_t dm = t.dm, pubm = t.pubm, privm = t.privm, npub = t.npub, r1 = t.r1;
+    const unsigned pev0 = t.pev0, pmsg0 = t.pmsg0;
+    if (!(t.nd && pev0 < c1 && pev0 + t.nd > c0)) return;
+    if (t.nsd) {
+        walk_events<S>(d, t, [&](unsigned at, unsigned m, uint32_t, int, int, EvFan ef) {
+            const unsigned a = pev0 + at;
+            if (a < c0 || a >= c1) return;
+            fan_ev_put(f.s_ev + 3u * (a - c0), pmsg0 + m, ef.pub ? (uint32_t)desc : (uint32_t)e, ef.n, r1, ef.pub);
+        });
+    } else {
+        // a runtime loop over the slots (an unrolled one gets hoisted out of the chunk loop
+        // and spills: 12 slots x 4 values)
+#pragma unroll 1
+        for (int j = 0; j < S::n_w(d); j++) {
+            if (!((dm >> j) & 1)) continue;
+            const uint32_t below = dm & S::u_lower(d, j);
+            const uint32_t at = pev0 + __builtin_popcount(below);
+            if (at < c0 || at >= c1) continue;
+            const bool pub = (pubm >> j) & 1;
+            const uint32_t m = pmsg0 + npub * __builtin_popcount(below & pubm) +
+                               __builtin_popcount(below & privm);
+            const uint32_t n = pub ? npub : ((privm >> j) & 1u);
+            fan_ev_put(f.s_ev + 3u * (at - c0), m, pub ? (uint32_t)desc : (uint32_t)e, n, r1, pub);
+        }
+    }
+}
+
+// Runs of 16 or more recipients, straight to HBM: n events of a chunk by lane groups of L/4 lanes
+// (L = the tile's largest recipient count rounded up to a power of two), four consecutive recipients
+// per lane in one 16-byte store (dword-aligned: runs start anywhere); consecutive events' runs are
+// adjacent, so a wave writes 64 x 16 B of one contiguous stretch
+template <class S>
+__device__ __forceinline__ void fan_lane_groups(const Dev& d, const FanLds& f, uint32_t* out, const uint32_t n_ev, const uint32_t L) {
+    const uint32_t L4 = L >= 4 ? L / 4 : 1u, sub4 = threadIdx.x & (L4 - 1);
+    for (uint32_t i = threadIdx.x / L4; i < n_ev; i += kTPB / L4) {
+        const FanEv ev = fan_ev_get(f.s_ev + 3 * i);
+        const uint32_t ms = ev.ms, n = ev.n;
+        if (!ev.pub) {  // private & !upload: the entity itself (n is 0 or 1)
+            if (sub4 == 0 && n) out[ms] = ev.a;
+            continue;
+        }
+        for (uint32_t p = 4 * sub4; p < n; p += 4 * L4) {  // every player of the group but self
+            uint32_t x[4];
+#pragma unroll
+            for (int q = 0; q < 4; q++) {
+                const uint32_t pq = p + (uint32_t)q;
+                x[q] = pq < n ? fan_player(d, f, ev.a, skip_self(pq, ev.r1)) : 0u;
+            }
+            if (p + 4 <= n) {
+                if constexpr ((S::kNt & kNtFanGroupStore) != 0)
+                    __builtin_nontemporal_store(u32x4_a4{x[0], x[1], x[2], x[3]}, (u32x4_a4*)(out + ms + p));
+                else
+                    *(u32x4_a4*)(out + ms + p) = u32x4_a4{x[0], x[1], x[2], x[3]};
+            } else {
+#pragma unroll
+                for (int q = 0; q < 3; q++)
+                    if (p + (uint32_t)q < n) out[ms + p + q] = x[q];
+            }
+        }
+    }
+}
+
+// Shorter runs: n events of a chunk written one thread per event into an LDS message window of W
+// words that is stored with 16-byte stores, in as many passes as the chunk's messages need (short
+// runs stored directly leave lines partly written by several waves, and lane groups would re-read
+// each event's triple once per lane).
+template <class S>
+__device__ __forceinline__ void fan_window(const Dev& d, const FanLds& f, uint32_t* out, const uint32_t n_ev, const unsigned W) {
+    const FanEv last = fan_ev_get(f.s_ev + 3u * (n_ev - 1u));
+    const unsigned m_lo = f.s_ev[0], m_hi = last.ms + last.n;
+    for (unsigned w0 = m_lo; w0 < m_hi; w0 += W) {  // uniform
+        const unsigned w1 = min(m_hi, w0 + W);
+        // short runs: one thread per event (fewer LDS reads than lane groups)
+        for (uint32_t i = threadIdx.x; i < n_ev; i += kTPB) {
+            const FanEv ev = fan_ev_get(f.s_ev + 3 * i);
+            const uint32_t ms = ev.ms, n = ev.n, r1 = ev.r1;
+            if (n == 0 || ms >= w1 || ms + n <= w0) continue;
+            if (!ev.pub) {
+                f.s_win[ms - w0] = ev.a;
+                continue;
+            }
+            const uint32_t np = n + (r1 ? 1u : 0u);
+            uint32_t k = ms;
+            for (uint32_t p = 0; p < np; p++) {
+                if (p + 1 == r1) continue;
+                if (k >= w0 && k < w1) f.s_win[k - w0] = fan_player(d, f, ev.a, p);
+                k++;
+            }
+        }
+        __syncthreads();
+        const uint32_t n = w1 - w0;
+        if ((w0 & 3u) == 0) {  // out is 16-byte aligned (msg_tcap is a multiple of 4): 16-byte stores
+            lds_flush16<(S::kNt & kNtFanStore) != 0>(out + w0, f.s_win, n);
+        } else {
+            for (uint32_t i = threadIdx.x; i < n; i += kTPB) out[w0 + i] = f.s_win[i];
+        }
+        __syncthreads();
+    }
+}
+
+// The tile's fan-out: the block-uniform choice of its form.  tev / tmsg: the tile's events and
+// messages; s_pb: the groups' player run [lo, hi) and the largest recipient count (tick_tile).
+template <int kU, class S>
+__device__ __forceinline__ void fan_out(const Dev& d, TickSt& t, const int tile, const unsigned tev, const unsigned tmsg,
+                                        const uint32_t* s_pb, uint64_t* s_o) {
+    const unsigned R = (unsigned)d.lds_words;
+    const uint32_t pb_lo = s_pb[0], npl = s_pb[1] > s_pb[0] ? s_pb[1] - s_pb[0] : 0u;
+    const uint32_t nm = s_pb[2];
+    const uint32_t L = nm <= 1 ? 1u : nm >= 64 ? 64u : 1u << (32 - __builtin_clz(nm - 1));
+    const bool win = L < ((d.ablate & kAblFanWin32) ? 64u : (d.ablate & kAblFanWin16) ? 32u : 16u);
+    const bool staged = npl <= R / 4;
+    const unsigned room = R - (staged ? npl : 0u);
+    // events per chunk: all of them, or what leaves the window half of the room
+    const unsigned ecap = (min(tev, win ? room / 6u : room / 3u) + 3u) & ~3u;
+    const unsigned W = win ? (room - 3u * ecap) & ~3u : 0u;  // window entries
+    FanLds f;
+    f.s_ev = (uint32_t*)s_o;
+    f.s_win = f.s_ev + 3u * ecap;
+    f.s_pl = f.s_ev + (R - npl);
+    f.pb_lo = pb_lo;
+    f.staged = staged;
+    uint32_t* out = d.msg_rcpt + (unsigned)tile * d.msg_tcap;
+    // NFGPU_ABLATE kAblFanTriples keeps the triples for every tile
+    const bool direct = win && staged && !(d.ablate & kAblFanTriples) && tmsg <= ((R - npl) & ~3u);
+    if (staged) {  // (the tally counts the run once for a direct tile too: summaries do not depend on the path)
+        if (!direct)
+            for (uint32_t i = threadIdx.x; i < npl; i += kTPB) f.s_pl[i] = (uint32_t)d.pl_slot[pb_lo + i];
+        t.bytes += 4 * ((npl + kTPB - 1 - threadIdx.x) / kTPB);
+    }
+    t.bytes += 4 * t.nmsg;
+    if (direct) {
+        fan_direct<kU, S>(d, t, (uint32_t*)s_o, out, tmsg, nm);
+        return;
+    }
+    for (unsigned c0 = 0; c0 < tev; c0 += ecap) {  // uniform: chunks of event triples
+        const unsigned c1 = min(tev, c0 + ecap);
+        fan_fill<S>(d, t, f, c0, c1);
+        __syncthreads();
+        if (win)
+            fan_window<S>(d, f, out, c1 - c0, W);
+        else
+            fan_lane_groups<S>(d, f, out, c1 - c0, L);
+        if (c1 < tev) __syncthreads();  // s_ev is refilled
+    }
 }
 
 // One tile of k_tick (the workgroup's; its LDS passed in).
 template <int kU, class S>
 __device__ __forceinline__ void tick_tile(const Dev& d, const int tile, unsigned long long* s_w, unsigned& s_bytes,
                                           uint32_t* s_pb, uint64_t* s_o) {
-    constexpr int kW = kU < kMaxW ? kU : kMaxW;  // writable register slots
     const int e = tile * kTile + (int)threadIdx.x;
-    if (d.tile_work && !d.tile_work[tile]) {  // (block-uniform) a calls-only pass, no Set group here:
-        if (d.has_recops && e < d.N) d.fired_mask[e] = 0;  // nothing fires, nothing is dirty
-        if (threadIdx.x == 0) {
-            d.t_ev[tile] = 0;
-            d.t_fi[tile] = 0;
-            d.t_msg[tile] = 0;
-        }
-        if (S::kLb && d.lb_rank) lb_publish(d, tile, 0u, 0u, 0u);
+    if (d.tile_work && !d.tile_work[tile]) {
+        tick_idle_tile<S>(d, tile, e);
         return;
     }
     const bool fuse = d.msg_tcap != 0;  // this tile's fan-out is written here, at tile * msg_tcap
@@ -541,523 +1105,62 @@ __device__ __forceinline__ void tick_tile(const Dev& d, const int tile, unsigned
     int32_t* s_rem = (int32_t*)(s_o + (size_t)S::n_w(d) * kTPB);  // [n_kind][kTPB] remain after a fire
     if (d.ablate & kAblCheckRem)  // (this thread's own column: read back only by this thread)
         for (int k = 0; k < S::n_kind(d); k++) s_rem[k * kTPB + threadIdx.x] = kRemUnset;
-    unsigned bytes = 0;
-    uint32_t fired = 0, xh = 0, wm = 0;
-    uint64_t desc = kDeadDesc;
+    TickSt t{};
+    t.e = e;
+    t.desc = kDeadDesc;
     uint64_t v[kU];
 #pragma unroll
     for (int j = 0; j < kU; j++) v[j] = 0;
-    {
-        // descriptor and schedule records in one round trip, without a branch: slots past N (the
-        // last tile) re-read slot N-1 and count as dead; a dead slot stores nothing
-        const int ec = e < d.N ? e : d.N - 1;
-        if constexpr (S::kSpecMask != 0) {
-            // a policy may load every program operand with the schedule records, before it knows
-            // which kinds fire: one round trip instead of two (sparse kinds' columns are read in
-            // lines that mostly have to be fetched anyway)
-            if (!(d.ablate & kAblNoLoads))
-#pragma unroll
-                for (int j = 0; j < kU; j++)
-                    if (((S::kSpecMask >> j) & 1) && !slot_is_cell<S>(d, j))
-                        v[j] = *elem<S>(d.u_col[j], (uint32_t)ec, S::u_str(d, j));
-        }
-        fired = sched_scan<S>(d, ec, bytes, desc, s_rem, e >= d.N);  // NFCScheduleModule::Execute (SM:51-81)
-        desc = e < d.N ? desc : kDeadDesc;
-        bytes = e < d.N ? bytes + 8 + 8u * (uint32_t)__builtin_popcount(S::kSpecMask) : 0u;
-    }
-    const bool live = !desc_dead(desc);
-    // queued Set groups of this slot (k_sets ran them): program destinations among them
-    uint32_t xset = 0;
-    if (live && d.n_x) {
-        xh = *elem<S>(d.ext_head, (uint32_t)e);
-        bytes += 4;
-        if (xh)
-            for (int g = (int)xh - 1; g < d.n_x && d.x_slot[g] == (uint32_t)e; g++) {
-                const uint32_t j = d.tab->w_slot[d.x_pid[g]];
-                xset |= j != kNoU ? 1u << j : 0u;
-                bytes += 8;
-            }
-    }
-    uint32_t need = 0, cu = 0;  // cu: the guard-cell slots whose row is used
-    if (live) {
-        need = xset;
-        if (!(d.ablate & kAblPrograms)) need |= S::need(d, fired);
-        // one batch of independent loads: every value this entity's frame reads or writes
-#pragma unroll
-        for (int j = 0; j < kU; j++)
-            if (((need >> j) & 1) && !((S::kSpecMask >> j) & 1) && !slot_is_cell<S>(d, j) && !(d.ablate & kAblNoLoads)) {
-                v[j] = ld_nt<(S::kNt & kNtColLoad) != 0>(elem<S>(d.u_col[j], (uint32_t)e, S::u_str(d, j)));
-                bytes += 8;
-            }
-        if (!(d.ablate & kAblNoLoads)) cu = cell_loads<kU, S>(d, e, need, v, bytes);
-    }
-    if (live) {
-#pragma unroll
-        for (int j = 0; j < kW; j++)
-            if (j < S::n_w(d) && ((need >> j) & 1)) s_o[j * kTPB + threadIdx.x] = v[j];
-        // a Set program destination: its frame-start value is the value before the Set group
-        if (xset) {
-            for (int g = (int)xh - 1; g < d.n_x && d.x_slot[g] == (uint32_t)e; g++) {
-                const uint32_t j = d.tab->w_slot[d.x_pid[g]];
-                if (j != kNoU) s_o[j * kTPB + threadIdx.x] = d.x_old[g];
-                bytes += j != kNoU ? 8 : 0;
-            }
-            wm = xset;
-        }
-        // the fired heartbeats' effect programs, in schedule-name order
-        wm |= cu << 16;  // (run_programs_u: the used guard cells take the walk's record ops)
-        if (!(d.ablate & (kAblPrograms | kAblNoRun)) && fired) S::run(v, wm, d, fired);
-    }
-    // dirty diff against the frame-start values
-    uint32_t dm = 0;
-#pragma unroll
-    for (int j = 0; j < kW; j++)
-        if (((wm >> j) & 1) && v[j] != s_o[j * kTPB + threadIdx.x]) dm |= 1u << j;
-    // a Set program destination that a program moved back to its frame-start value has no event,
-    // but k_sets changed its column: write it back here (the dirty slots are written with their
-    // events)
-    if (xset & ~dm)
-#pragma unroll
-        for (int j = 0; j < kW; j++)
-            if (j < S::n_w(d) && ((xset & ~dm) >> j) & 1) {
-                *elem<S>(d.u_col[j], (uint32_t)e, S::u_str(d, j)) = v[j];
-                bytes += 8;
-            }
-    // fan-out message counts (event_msgs): a public property's event goes to every player of the
-    // group but the entity itself, a private & !upload one to the entity only.  The message offset
-    // of a slot's event = the counts of the dirty slots with lower property ids (Dev::u_lower).
-    // the entity's class's event masks (Dev::u_cmask; class 15, a free slot: no slots): a select
-    // over kernel-argument scalars, no indexed copy and no barrier
-    const uint32_t cm = S::class_mask(d, (unsigned)(desc >> 60));
-    const uint32_t pubm = cm & 0xFFFFu, privm = cm >> 16;
-    const uint32_t r1 = (uint32_t)((desc >> 46) & 0x3FFF);
-    const uint32_t npub = (uint32_t)((desc >> 32) & 0x3FFF) - (r1 ? 1u : 0u);
-    unsigned nmsg = npub * __builtin_popcount(dm & pubm) + __builtin_popcount(dm & privm);
-    unsigned nmax = (dm & pubm) ? npub : ((dm & privm) ? 1u : 0u);
-    unsigned nd = __builtin_popcount(dm);
-    // standalone Set events (properties no program writes): counted here, merged in property-id
-    // order with the slots' events below
-    unsigned nsd = 0;
-    if (xh) {
-        for (int g = next_standalone(d, (int)xh - 1, e); g < d.n_x; g = next_standalone(d, g + 1, e)) {
-            const EvFan f = ev_fan(d, desc, d.x_pid[g]);
-            nsd++;
-            nmsg += f.n;
-            nmax = max(nmax, f.n);
-            bytes += 8;
-        }
-        nd += nsd;
-    }
-    // the entity's events in property-id order: dirty slots (u_order) merged with the standalone
-    // groups; emit(rank, message offset, pid, slot or -1, group, recipients) per event
-    auto walk = [&](auto&& emit) {
-        int g = next_standalone(d, (int)xh - 1, e);
-        unsigned at = 0, m = 0;
-#pragma unroll 1
-        for (int i = 0; i <= S::n_w(d); i++) {
-            const int j = i < S::n_w(d) ? S::u_order(d, i) : -1;
-            const uint32_t pj = j >= 0 ? (uint32_t)S::u_pid(d, j) : 0xFFFFFFFFu;
-            while (g < d.n_x && d.x_pid[g] < pj) {
-                const EvFan f = ev_fan(d, desc, d.x_pid[g]);
-                emit(at, m, d.x_pid[g], -1, g, f);
-                at++;
-                m += f.n;
-                g = next_standalone(d, g + 1, e);
-            }
-            if (j >= 0 && ((dm >> j) & 1)) {
-                const bool pub = (pubm >> j) & 1;
-                const EvFan f{pub ? npub : ((privm >> j) & 1u), pub};
-                emit(at, m, pj, j, 0, f);
-                at++;
-                m += f.n;
-            }
-        }
-    };
-    const unsigned nf = __builtin_popcount(fired);
-    const uint32_t dm_ = dm;
+    tick_load_run<kU, S>(d, t, v, s_o, s_rem);
+    tick_counts<S>(d, t);
     // tile-local compaction: one block scan of (fired:16 | events:16 | messages:32)
+    const unsigned nf = __builtin_popcount(t.fired);
     unsigned long long tot;
     const unsigned long long excl =
-        block_excl_scan(((unsigned long long)nf << 48) | ((unsigned long long)nd << 32) | nmsg, s_w, tot);
-    const unsigned pev0 = (unsigned)((excl >> 32) & 0xFFFF);
-    unsigned pfi = (unsigned)(excl >> 48);
-    const unsigned pmsg0 = (unsigned)excl, tmsg = (unsigned)tot;
+        block_excl_scan(((unsigned long long)nf << 48) | ((unsigned long long)t.nd << 32) | t.nmsg, s_w, tot);
+    t.pev0 = (unsigned)((excl >> 32) & 0xFFFF);
+    t.pfi = (unsigned)(excl >> 48);
+    t.pmsg0 = (unsigned)excl;
+    const unsigned tmsg = (unsigned)tot;
     // (after the scan: its barrier orders thread 0's s_pb initialisation before these atomics, and
     // the barrier before the fan-out orders them before its reads)
     if (fuse) {  // the pl_slot run of the groups whose members have messages (they are contiguous)
-        const uint32_t np = (uint32_t)((desc >> 32) & 0x3FFF);
-        uint32_t lo = nmsg ? (uint32_t)desc : 0xFFFFFFFFu, hi = nmsg ? (uint32_t)desc + np : 0u;
-#pragma unroll
-        for (int m = 32; m >= 1; m >>= 1) {
-            lo = min(lo, (uint32_t)__shfl_xor((int)lo, m, 64));
-            hi = max(hi, (uint32_t)__shfl_xor((int)hi, m, 64));
-            nmax = max(nmax, (uint32_t)__shfl_xor((int)nmax, m, 64));
-        }
+        const uint32_t np = (uint32_t)((t.desc >> 32) & 0x3FFF);
+        uint32_t lo = t.nmsg ? (uint32_t)t.desc : 0xFFFFFFFFu, hi = t.nmsg ? (uint32_t)t.desc + np : 0u;
+        fan_run_reduce(lo, hi, t.nmax);
         if ((threadIdx.x & 63) == 0 && hi) {
             atomicMin(&s_pb[0], lo);
             atomicMax(&s_pb[1], hi);
-            atomicMax(&s_pb[2], nmax);
+            atomicMax(&s_pb[2], t.nmax);
         }
     }
-    // this tile's counts for the dense ranks, as early as they are known (the rank workgroups poll them)
     // this tile's output runs (wave-uniform bases, tile-local 32-bit offsets)
     const size_t ev0 = (size_t)tile * d.ev_tcap, fi0 = (size_t)tile * d.fi_tcap;
-    uint32_t* const t_evm = d.ev_moff + ev0;
-
-    if (live) {
-        // write back the changed values; their events in property-id order (rank among the
-        // entity's dirty slots by Dev::u_lower)
-        if (nd && !(d.ablate & kAblNoEmit)) {
-            uint32_t* const t_evs = d.ev_slot + ev0;
-            uint32_t* const t_evp = d.ev_pid + ev0;
-            uint64_t* const t_evo = d.ev_old + ev0;
-            uint64_t* const t_evn = d.ev_new + ev0;
-            if (!nsd) {
-                // A thread's events sit at consecutive ranks, so two consecutive ones are stored
-                // together (8-byte stores of the slot and pid words, 16-byte stores of the old and
-                // new values, at any dword): one store per array covers most of a wave's run instead
-                // of one per event slot with the lanes ~2.4 events apart
-                // (tools/event_store_probe.hip: 22.4 -> 18.8 us for config[1]'s 2.5M events)
-                constexpr bool kNE = (S::kNt & kNtEventStore) != 0;
-                bool pend = false;  // an event held back to be stored with the next one
-                uint32_t pa = 0, pp = 0;
-                uint64_t po = 0, pn = 0;
-#pragma unroll
-                for (int j = 0; j < kW; j++) {
-                    if (j >= S::n_w(d) || !((dm >> j) & 1)) continue;
-                    const uint32_t below = dm & S::u_lower(d, j);
-                    const uint32_t at = pev0 + __builtin_popcount(below);
-                    const uint64_t nv = v[j], ov = s_o[j * kTPB + threadIdx.x];
-                    const uint32_t pid = (uint32_t)S::u_pid(d, j);
-                    if (!(d.ablate & kAblNoWriteBack)) st_nt<(S::kNt & kNtStateStore) != 0>(elem<S>(d.u_col[j], (uint32_t)e, S::u_str(d, j)), nv);
-                    if (!fuse)  // tile-local; k_fanout adds the tile's message base
-                        st_off(t_evm, at, pmsg0 + npub * __builtin_popcount(below & pubm) +
-                                              __builtin_popcount(below & privm));
-                    if (d.ablate & kAblNoEvStore) {
-                    } else if (pend && at == pa + 1) {  // (the writable slots are in property-id order)
-                        st_vec<kNE>(t_evs, 4u * pa, u32x2_a4{(uint32_t)e, (uint32_t)e});
-                        st_vec<kNE>(t_evp, 4u * pa, u32x2_a4{pp, pid});
-                        st_vec<kNE>(t_evo, 8u * pa, u32x4_a4{(uint32_t)po, (uint32_t)(po >> 32), (uint32_t)ov, (uint32_t)(ov >> 32)});
-                        st_vec<kNE>(t_evn, 8u * pa, u32x4_a4{(uint32_t)pn, (uint32_t)(pn >> 32), (uint32_t)nv, (uint32_t)(nv >> 32)});
-                        pend = false;
-                    } else {
-                        if (pend) {
-                            st_off_nt<kNE>(t_evs, pa, (uint32_t)e);
-                            st_off_nt<kNE>(t_evp, pa, pp);
-                            st_off_nt<kNE>(t_evo, pa, po);
-                            st_off_nt<kNE>(t_evn, pa, pn);
-                        }
-                        pend = true;
-                        pa = at;
-                        pp = pid;
-                        po = ov;
-                        pn = nv;
-                    }
-                    bytes += 8 + 24;
-                }
-                if (pend && !(d.ablate & kAblNoEvStore)) {
-                    st_off_nt<kNE>(t_evs, pa, (uint32_t)e);
-                    st_off_nt<kNE>(t_evp, pa, pp);
-                    st_off_nt<kNE>(t_evo, pa, po);
-                    st_off_nt<kNE>(t_evn, pa, pn);
-                }
-            } else {
-                // (rare: an entity with standalone Set events) write back the slots, then every
-                // event by the merged walk, which reads the slots' new values back from their
-                // columns so that no register of the working set stays live in it
-#pragma unroll
-                for (int j = 0; j < kW; j++)
-                    if (j < S::n_w(d) && ((dm >> j) & 1)) {
-                        *elem<S>(d.u_col[j], (uint32_t)e, S::u_str(d, j)) = v[j];
-                        bytes += 8;
-                    }
-                walk([&](unsigned at, unsigned m, uint32_t pid, int j, int g, EvFan) {
-                    uint64_t ov, nv;
-                    if (j >= 0) {
-                        ov = s_o[j * kTPB + threadIdx.x];
-                        nv = __hip_atomic_load(elem<S>(d.u_col[j], (uint32_t)e, S::u_str(d, j)), __ATOMIC_RELAXED,
-                                               __HIP_MEMORY_SCOPE_WAVEFRONT);
-                    } else {  // (k_sets wrote the column)
-                        ov = d.x_old[g];
-                        nv = d.x_new[g];
-                        if ((int)pid >= d.n_if) {  // an object property: its head halves beside
-                            st_off(d.ev_old_h + ev0, pev0 + at, d.x_old_h[g]);
-                            st_off(d.ev_new_h + ev0, pev0 + at, d.x_new_h[g]);
-                            bytes += 16;
-                        }
-                    }
-                    st_off(t_evs, pev0 + at, (uint32_t)e);
-                    st_off(t_evp, pev0 + at, pid);
-                    st_off(t_evo, pev0 + at, ov);
-                    st_off(t_evn, pev0 + at, nv);
-                    if (!fuse) st_off(t_evm, pev0 + at, pmsg0 + m);
-                    bytes += 24;
-                });
-            }
-        }
-        uint32_t* const t_fis = d.fi_slot + fi0;
-        uint32_t* const t_fik = d.fi_kind + fi0;
-        int32_t* const t_fir = d.fi_remain + fi0;
-        uint32_t fl = fired;
-        while (fl) {
-            const int k = __builtin_ctz(fl);
-            fl &= fl - 1;
-            constexpr bool kNE = (S::kNt & kNtEventStore) != 0;
-            const int32_t rem = s_rem[k * kTPB + threadIdx.x];
-            // (a forever heartbeat's remain may be any int32, the sentinel too: sched_edges worlds
-            // wrap it through INT32_MIN; a counted one is >= 0 after a fire.  The forever bit is the
-            // same before and after the scan, so the record's state is read whatever the L1 holds)
-            if ((d.ablate & kAblCheckRem) && rem == kRemUnset &&
-                !(elem<S>(d.s_hot + (size_t)k * d.s_kstr, (uint32_t)e)->state & kStForever))
-                dev_error(d, kErrRemain);
-            if (!(d.ablate & kAblNoFiStore)) {
-                st_off_nt<kNE>(t_fis, pfi, (uint32_t)e);
-                st_off_nt<kNE>(t_fik, pfi, (uint32_t)k);
-                st_off_nt<kNE>(t_fir, pfi, rem);
-            }
-            pfi++;
-            bytes += 12;
-        }
-        if (xh) *elem<S>(d.ext_head, (uint32_t)e) = 0;
+    if (!desc_dead(t.desc)) {
+        // (the three are independent: the slot's Set groups were read through t.xh, the fired list
+        // reads s_rem, the events read v and s_o.  This order is the one that spills least in the
+        // library's instantiations: profiles/r20a_tick_phases.txt)
+        if (t.xh) *elem<S>(d.ext_head, (uint32_t)e) = 0;
+        emit_fired<S>(d, t, s_rem, fi0);
+        if (t.nd && !(d.ablate & kAblNoEmit)) emit_events<kU, S>(d, t, v, s_o, ev0, fuse);
     }
     if (d.has_recops && e < d.N) {  // slack slots too: a slot's previous occupant left a mask
-        *elem<S>(d.fired_mask, (uint32_t)e) = fired;
-        bytes += 4;
+        *elem<S>(d.fired_mask, (uint32_t)e) = t.fired;
+        t.bytes += 4;
     }
-    if (!fuse && !(d.ablate & kAblNoEmit)) bytes += 4 * nd;  // ev_moff
-    // Fan-out of the tile's events (GetBroadCastObject, AOI:531-593; see k_fanout), into the
-    // tile's fixed-stride run mb.  The LDS region of the frame-start image is reused for a chunk
-    // of the tile's events as (first message, first player | slot, count | rank | public) triples
-    // and the groups' player run; each event is then expanded by a group of L lanes (L = the
-    // tile's largest recipient count rounded up to a power of two), so consecutive lane groups
-    // store consecutive events' runs.  Runs of 16 or more recipients are stored that way straight
-    // to HBM; shorter ones are written one thread per event into an LDS message window stored
-    // with 16-byte stores (short runs stored directly leave lines partly written by several
-    // waves, and lane groups would re-read each event's triple once per lane).
+    if (!fuse && !(d.ablate & kAblNoEmit)) t.bytes += 4 * t.nd;  // ev_moff
     if (fuse) {
         __syncthreads();  // s_pb; every read of s_o and s_rem is done: the region is reused
-        uint32_t dm = dm_;
-        const unsigned mb = (unsigned)tile * d.msg_tcap;
         const unsigned tev = (unsigned)((tot >> 32) & 0xFFFF);
-        const bool fan = tmsg && tmsg <= d.msg_tcap;
         if (tmsg > d.msg_tcap && threadIdx.x == 0) dev_error(d, kErrFanBound);  // (host bound)
         // this tile's counts for the dense ranks (the rank workgroups poll them while the fan-out runs)
         if (S::kLb && d.lb_rank) lb_publish(d, tile, tev, (unsigned)(tot >> 48), tmsg);
         // No per-event message offsets: the tile's run holds its events' recipients in event order
         // (the readers count through it: k_counted_moff)
-        if (fan) {
-            const unsigned R = (unsigned)d.lds_words;
-            const uint32_t pb_lo = s_pb[0], npl = s_pb[1] > s_pb[0] ? s_pb[1] - s_pb[0] : 0u;
-            const uint32_t nm = s_pb[2];
-            const uint32_t L = nm <= 1 ? 1u : nm >= 64 ? 64u : 1u << (32 - __builtin_clz(nm - 1));
-            const uint32_t sub = threadIdx.x & (L - 1);
-            const bool win = !(d.ablate & kAblFanNoWin) &&
-                             L < ((d.ablate & kAblFanWin32) ? 64u : (d.ablate & kAblFanWin16) ? 32u : 16u);
-            const bool staged = npl <= R / 4;
-            const unsigned room = R - (staged ? npl : 0u);
-            // events per chunk: all of them, or what leaves the window half of the room
-            const unsigned ecap = (min(tev, win ? room / 6u : room / 3u) + 3u) & ~3u;
-            const unsigned W = win ? (room - 3u * ecap) & ~3u : 0u;  // window entries
-            uint32_t* s_ev = (uint32_t*)s_o;
-            uint32_t* s_win = s_ev + 3u * ecap;
-            uint32_t* s_pl = s_ev + (R - npl);
-            uint32_t* out = d.msg_rcpt + mb;
-            const bool direct = win && staged && !(d.ablate & kAblFanTriples) && tmsg <= ((R - npl) & ~3u);
-            if (staged) {  // (the tally counts the run once for a direct tile too: summaries do not depend on the path)
-                if (!direct)
-                    for (uint32_t i = threadIdx.x; i < npl; i += kTPB) s_pl[i] = (uint32_t)d.pl_slot[pb_lo + i];
-                bytes += 4 * ((npl + kTPB - 1 - threadIdx.x) / kTPB);
-            }
-            bytes += 4 * nmsg;
-            // Short runs whose tile's whole run would fit beside the staged players: no triples, no
-            // event loop and no window passes.  A thread knows its own events and their message
-            // offsets, so it writes their recipients straight into the window [0, tmsg) at s_o
-            // (tile-local offsets), and the window is stored once.  The players are read from
-            // pl_slot through L1 (a group's run is read by its ~250 neighbouring threads), which
-            // saves the staging and its barrier.  Block-uniform; NFGPU_ABLATE kAblFanTriples keeps
-            // the triples for every tile.
-            if (direct) {
-                uint32_t* const s_run = (uint32_t*)s_o;
-                if (nsd) {  // (rare) the merged walk gives each event's offset and recipients
-                    walk([&](unsigned, unsigned m, uint32_t, int, int, EvFan f) {
-                        uint32_t* w = s_run + pmsg0 + m;
-                        if (!f.pub) {
-                            if (f.n) w[0] = (uint32_t)e;
-                            return;
-                        }
-                        const auto* pl = d.pl_slot + (uint32_t)desc;
-                        for (uint32_t k = 0; k < f.n; k++) w[k] = (uint32_t)pl[k + ((r1 && k + 1 >= r1) ? 1u : 0u)];
-                    });
-                } else if (nmsg) {
-                    // public events with recipients: the q-th one's run starts npub * q + (the
-                    // private events before it: 4 bits each in pk) words after the thread's first
-                    const uint32_t dpub = npub ? dm & pubm : 0u, dprv = dm & privm;
-                    unsigned long long pk = 0;
-                    if (dprv) {  // a private event goes to the entity itself
-#pragma unroll
-                        for (int j = 0; j < kW; j++) {
-                            if (j >= S::n_w(d)) continue;
-                            const uint32_t below = dm & S::u_lower(d, j);
-                            const uint32_t q = __builtin_popcount(below & pubm), pv = __builtin_popcount(below & privm);
-                            if ((dprv >> j) & 1) s_run[pmsg0 + npub * q + pv] = (uint32_t)e;
-                            pk |= ((dpub >> j) & 1) ? (unsigned long long)pv << (4u * q) : 0ull;
-                        }
-                    }
-                    const uint32_t npe = __builtin_popcount(dpub);
-                    if (npe) {
-                        // eight recipients at a time, read once and written to every public event's
-                        // run: a store past a run's end repeats its last word (the same value at the
-                        // same place), so only the event loop's trip count differs between lanes
-                        const auto* pl = d.pl_slot + (uint32_t)desc;
-#pragma unroll 1
-                        for (uint32_t k0 = 0; k0 < nm; k0 += 8) {  // uniform
-                            uint32_t x[8], o[8];
-#pragma unroll
-                            for (int k = 0; k < 8; k++) {  // every player of the group but self
-                                o[k] = min(k0 + (uint32_t)k, npub - 1u);
-                                x[k] = (uint32_t)pl[o[k] + ((r1 && o[k] + 1 >= r1) ? 1u : 0u)];
-                            }
-                            uint32_t* w = s_run + pmsg0;
-                            unsigned long long t = pk;
-                            for (uint32_t q = 0; q < npe; q++) {
-                                uint32_t* wq = w + ((uint32_t)t & 15u);
-#pragma unroll
-                                for (int k = 0; k < 8; k++) wq[o[k]] = x[k];
-                                w += npub;
-                                t >>= 4;
-                            }
-                        }
-                    }
-                }
-                __syncthreads();
-                // mb is a multiple of 4 (msg_tcap is): 16-byte stores; nothing refills the window
-                const uint32_t n4 = tmsg >> 2;
-                uint4* dst4 = (uint4*)out;
-                const uint4* src4 = (const uint4*)s_run;
-                for (uint32_t i = threadIdx.x; i < n4; i += kTPB) st_nt<(S::kNt & kNtFanStore) != 0>(dst4 + i, src4[i]);
-                if (threadIdx.x < (tmsg & 3u)) out[4 * n4 + threadIdx.x] = s_run[4 * n4 + threadIdx.x];
-            } else  // chunks of event triples (the code below keeps its indentation)
-            for (unsigned c0 = 0; c0 < tev; c0 += ecap) {  // uniform
-                const unsigned c1 = min(tev, c0 + ecap);
-                // a runtime loop over the slots (an unrolled one gets hoisted out of the chunk loop
-                // and spills: 12 slots x 4 values)
-                if (nd && pev0 < c1 && pev0 + nd > c0) {
-                    if (nsd) {
-                        walk([&](unsigned at, unsigned m, uint32_t, int, int, EvFan f) {
-                            const unsigned a = pev0 + at;
-                            if (a < c0 || a >= c1) return;
-                            uint32_t* x = s_ev + 3u * (a - c0);
-                            x[0] = pmsg0 + m;
-                            x[1] = f.pub ? (uint32_t)desc : (uint32_t)e;
-                            x[2] = f.n | (r1 << 14) | (f.pub ? 0x80000000u : 0u);
-                        });
-                    } else {
-#pragma unroll 1
-                        for (int j = 0; j < S::n_w(d); j++) {
-                            if (!((dm >> j) & 1)) continue;
-                            const uint32_t below = dm & S::u_lower(d, j);
-                            const uint32_t at = pev0 + __builtin_popcount(below);
-                            if (at < c0 || at >= c1) continue;
-                            const bool pub = (pubm >> j) & 1;
-                            const uint32_t m = pmsg0 + npub * __builtin_popcount(below & pubm) +
-                                               __builtin_popcount(below & privm);
-                            const uint32_t n = pub ? npub : ((privm >> j) & 1u);
-                            uint32_t* x = s_ev + 3u * (at - c0);
-                            x[0] = m;
-                            x[1] = pub ? (uint32_t)desc : (uint32_t)e;
-                            x[2] = n | (r1 << 14) | (pub ? 0x80000000u : 0u);
-                        }
-                    }
-                }
-                __syncthreads();
-                if (!win && !(d.ablate & kAblFan1)) {
-                    // lane groups of L/4 lanes, four consecutive recipients per lane in one 16-byte
-                    // store (dword-aligned: runs start anywhere); consecutive events' runs are
-                    // adjacent, so a wave writes 64 x 16 B of one contiguous stretch
-                    const uint32_t L4 = L >= 4 ? L / 4 : 1u, sub4 = threadIdx.x & (L4 - 1);
-                    for (uint32_t i = threadIdx.x / L4; i < c1 - c0; i += kTPB / L4) {
-                        const uint32_t ms = s_ev[3 * i], a = s_ev[3 * i + 1], b = s_ev[3 * i + 2];
-                        const uint32_t n = b & 0x3FFFu, r1 = (b >> 14) & 0x3FFFu;
-                        if (!(b >> 31)) {  // private & !upload: the entity itself (n is 0 or 1)
-                            if (sub4 == 0 && n) out[ms] = a;
-                            continue;
-                        }
-                        for (uint32_t p = 4 * sub4; p < n; p += 4 * L4) {  // every player of the group but self
-                            uint32_t x[4];
-#pragma unroll
-                            for (int q = 0; q < 4; q++) {
-                                const uint32_t pq = p + (uint32_t)q;
-                                const uint32_t pp = pq + ((r1 && pq + 1 >= r1) ? 1u : 0u);
-                                x[q] = pq < n ? (staged ? s_pl[a - pb_lo + pp] : (uint32_t)d.pl_slot[a + pp]) : 0u;
-                            }
-                            if (p + 4 <= n) {
-                                if constexpr ((S::kNt & kNtFanGroupStore) != 0)
-                                    __builtin_nontemporal_store(u32x4_a4{x[0], x[1], x[2], x[3]}, (u32x4_a4*)(out + ms + p));
-                                else
-                                    *(u32x4_a4*)(out + ms + p) = u32x4_a4{x[0], x[1], x[2], x[3]};
-                            } else {
-#pragma unroll
-                                for (int q = 0; q < 3; q++)
-                                    if (p + (uint32_t)q < n) out[ms + p + q] = x[q];
-                            }
-                        }
-                    }
-                } else if (!win) {
-                    for (uint32_t i = threadIdx.x / L; i < c1 - c0; i += kTPB / L) {
-                        const uint32_t ms = s_ev[3 * i], a = s_ev[3 * i + 1], b = s_ev[3 * i + 2];
-                        const uint32_t n = b & 0x3FFFu, r1 = (b >> 14) & 0x3FFFu;
-                        if (!(b >> 31)) {  // private & !upload: the entity itself (n is 0 or 1)
-                            if (sub < n) out[ms] = a;
-                            continue;
-                        }
-                        for (uint32_t p = sub; p < n; p += L) {  // every player of the group but self
-                            const uint32_t pp = p + ((r1 && p + 1 >= r1) ? 1u : 0u);
-                            out[ms + p] = staged ? s_pl[a - pb_lo + pp] : (uint32_t)d.pl_slot[a + pp];
-                        }
-                    }
-                } else {
-                    const unsigned last = 3u * (c1 - c0 - 1u);
-                    const unsigned m_lo = s_ev[0], m_hi = s_ev[last] + (s_ev[last + 2] & 0x3FFFu);
-                    for (unsigned w0 = m_lo; w0 < m_hi; w0 += W) {  // uniform
-                        const unsigned w1 = min(m_hi, w0 + W);
-                        // short runs: one thread per event (fewer LDS reads than lane groups)
-                        for (uint32_t i = threadIdx.x; i < c1 - c0; i += kTPB) {
-                            const uint32_t ms = s_ev[3 * i], a = s_ev[3 * i + 1], b = s_ev[3 * i + 2];
-                            const uint32_t n = b & 0x3FFFu, r1 = (b >> 14) & 0x3FFFu;
-                            if (n == 0 || ms >= w1 || ms + n <= w0) continue;
-                            if (!(b >> 31)) {
-                                s_win[ms - w0] = a;
-                                continue;
-                            }
-                            const uint32_t np = n + (r1 ? 1u : 0u);
-                            uint32_t k = ms;
-                            for (uint32_t p = 0; p < np; p++) {
-                                if (p + 1 == r1) continue;
-                                if (k >= w0 && k < w1)
-                                    s_win[k - w0] = staged ? s_pl[a - pb_lo + p] : (uint32_t)d.pl_slot[a + p];
-                                k++;
-                            }
-                        }
-                        __syncthreads();
-                        const uint32_t n = w1 - w0;
-                        if ((w0 & 3u) == 0) {  // mb is a multiple of 4 (msg_tcap is): 16-byte stores
-                            const uint32_t n4 = n >> 2;
-                            uint4* dst4 = (uint4*)(out + w0);
-                            const uint4* src4 = (const uint4*)s_win;
-                            for (uint32_t i = threadIdx.x; i < n4; i += kTPB) st_nt<(S::kNt & kNtFanStore) != 0>(dst4 + i, src4[i]);
-                            if (threadIdx.x < (n & 3u)) out[w0 + 4 * n4 + threadIdx.x] = s_win[4 * n4 + threadIdx.x];
-                        } else {
-                            for (uint32_t i = threadIdx.x; i < n; i += kTPB) out[w0 + i] = s_win[i];
-                        }
-                        __syncthreads();
-                    }
-                }
-                if (c1 < tev) __syncthreads();  // s_ev is refilled
-            }
-        }
+        if (tmsg && tmsg <= d.msg_tcap) fan_out<kU, S>(d, t, tile, tev, tmsg, s_pb, s_o);
     }
     // tile counts and algorithmic-byte tally
-    const unsigned wb = (unsigned)wave_sum(bytes);
+    const unsigned wb = (unsigned)wave_sum(t.bytes);
     if ((threadIdx.x & 63) == 0) atomicAdd(&s_bytes, wb);
     __syncthreads();
     if (threadIdx.x == 0) {
@@ -1082,8 +1185,7 @@ __global__ __launch_bounds__(kTPB) __attribute__((amdgpu_waves_per_eu(kWPE, 8)))
             return;
         }
     }
-    const int tile = d.xcd_map ? xcd_tile((int)blockIdx.x, d.n_tiles) : (int)blockIdx.x;
-    tick_tile<kU, S>(d, tile, s_w, s_bytes, s_pb, s_o);
+    tick_tile<kU, S>(d, xcd_tile((int)blockIdx.x, d.n_tiles), s_w, s_bytes, s_pb, s_o);
 }
 
 

@@ -88,6 +88,10 @@ def test_direct_and_windowed_tiles_in_one_frame(gpu_available, monkeypatch, jit)
     print("window", R, "players", players, "tile messages", sorted(c))
     assert ((c > 0) & (c <= ((R - players) & ~3))).any(), "no tile fits the direct window"
     assert (c > R).any(), "no tile falls back to the window passes"
+    # a chunk of triples holds at most R / 6 events (rounded up to 4) when the window takes the other half
+    ev = np.concatenate([np.diff(got[f"rk_t{t}_ev_base"][:nt + 1].astype(np.int64)) for t, nt in enumerate(tiles)])
+    print("tile events", sorted(ev)[-4:], "chunk capacity", (R // 6 + 3) & ~3)
+    assert (ev > ((R // 6 + 3) & ~3)).any(), "no tile takes several chunks of triples"
 
 
 @pytest.mark.parametrize("ablate", [0, FAN_WIN16], ids=["win8", "win16"])
@@ -123,3 +127,24 @@ def test_private_properties_only(gpu_available, monkeypatch, jit):
     w["tick_time"] = np.full(len(w["tick_time"]), np.iinfo(np.int64).min, np.int64)
     got, tiles = check(monkeypatch, w, jit)
     assert msg_counts(got, tiles).max() > 0
+
+
+NO_FUSE = 4096          # kAblNoFuse: the fan-out in k_fanout, after k_tick (outputs exact)
+K_FAN_LDS = 2048        # kFanLds: the players k_fanout stages in LDS
+R_MAX = 7424            # the largest LDS share of k_tick in words: (163840 / 5 - 2560 rounded down to 1 KiB) / 4
+
+
+@JIT
+def test_a_player_run_too_long_to_stage(gpu_available, monkeypatch, jit):
+    """one group of 2100 players: above k_fanout's kFanLds = 2048 staged players and above a quarter of
+    the largest LDS share k_tick gets at 5 waves per SIMD (7424 words: 1856), so every tile expands its
+    runs from the players in global memory; once more with the fan-out in k_fanout"""
+    w = workload.make_world(n_obj=2400, n_scenes=1, groups_per_scene=1, players_per_group=2100, n_ticks=2, seed=59)
+    assert len(np.unique(w["scene"])) == 1 and len(np.unique(w["group"])) == 1   # the only group
+    players = int(w["is_player"].sum())
+    assert players == 2100 and players > K_FAN_LDS and players > R_MAX // 4
+    ref = run_oracle(w)
+    check(monkeypatch, w, jit)
+    monkeypatch.setenv("NFGPU_ABLATE", str(NO_FUSE))
+    got, _, _ = run_frames(w)
+    compare_runs(got, ref)

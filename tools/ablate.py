@@ -1,6 +1,7 @@
-"""Interleaved A/B timing of k_tick / k_fanout variants in ONE process (timing-only
-ablations via NFGPU_ABLATE; outputs of ablated variants are not valid).
-    python tools/ablate.py [--variants 0,1,2,4] [--rounds 5] [--frames 20]"""
+"""Interleaved A/B timing of k_tick / k_fanout variants in ONE process: each variant is a value of
+NFGPU_ABLATE, the switches listed in csrc/nfgpu_device.hpp (timing only, outputs invalid: 4, 128,
+256, 512, 1024, 2048, 1<<18, 1<<19; exact variants: 8, 32, 4096, 1<<16, 1<<24, 1<<25, 1<<28).
+    python tools/ablate.py [--variants 0,4,2048,4096] [--rounds 5] [--frames 20]"""
 import argparse
 import json
 import os
