@@ -462,6 +462,34 @@ public:
     // entities, or with a shard attached every shard's (collective then: SceneShard::RankTop) ----
     bool GetRange(const std::string& prop, int k, std::vector<std::pair<std::string, double>>& memberScoreVec);
 
+    // ---- scene queries: NFCKernelModule::GetObjectByProperty (KM:1357-1405), the GetGroupObjectList
+    // overloads (KM:1169-1294), GetSceneOnLineList / GetSceneOnLineCount (KM:1042-1102), GetOnLineCount
+    // (KM:1015), NFIDataList as std::vector<NFGUID> (appended to, as the reference's list.Add).  One
+    // device query each (nfk_query_objects), lists in the reference's order: group id, then NFGUID.
+    // The buffered SetProperty* and schedule calls are flushed first, so the answer is the
+    // reference's now (read-your-writes).  GetObjectByProperty: an int argument on an int property
+    // or an object argument on an object property is compared on the device over the scene's players
+    // whose class has the property (SetPropertyFlags named it for the class; a property no class
+    // names: every class); every other combination follows the reference's getters, which read the
+    // null value through a getter of another type — an int argument on a float / object property
+    // matches every such player iff it is 0, an object argument on an int / float property iff it is
+    // the null NFGUID, a float (or string) argument matches nothing (`default:`, KM:1398).  Returns
+    // list.size() (the reference's list.GetCount()).  GetGroupObjectList returns false for a scene
+    // group this world does not hold.  With a shard attached every call answers for this shard's
+    // scenes only (no cross-shard gather).  They throw std::runtime_error when the nfgpu library
+    // loaded has no nfk_query_objects, as every failed C-ABI call does.
+    int GetObjectByProperty(int nSceneID, const std::string& strPropertyName, const TData& valueArg,
+                            std::vector<NFGUID>& list);
+    bool GetGroupObjectList(int nSceneID, int nGroupID, std::vector<NFGUID>& list);
+    bool GetGroupObjectList(int nSceneID, int nGroupID, std::vector<NFGUID>& list, bool bPlayer);
+    bool GetGroupObjectList(int nSceneID, int nGroupID, const std::string& strClassName, std::vector<NFGUID>& list);
+    bool GetGroupObjectList(int nSceneID, int nGroupID, const std::string& strClassName, const NFGUID& noSelf,
+                            std::vector<NFGUID>& list);
+    int GetSceneOnLineList(int nSceneID, std::vector<NFGUID>& list);
+    int GetSceneOnLineCount(int nSceneID);
+    int GetSceneOnLineCount(int nSceneID, int nGroupID);
+    int GetOnLineCount();
+
     // ---- NFISceneAOIModule recipient-list events ----
     bool AddPropertyEventCallBack(const PROPERTY_SINGLE_EVENT_FUNCTOR& cb);
     bool AddRecordEventCallBack(const RECORD_SINGLE_EVENT_FUNCTOR& cb);
@@ -548,6 +576,11 @@ public:
 
 private:
     void check(int rc, const char* what) const;
+    // one nfk_query_objects batch (the entry point resolved at first use); the hits of all its
+    // queries appended to list in query order; exists[0] of the batch
+    bool RunQueries(const nfk_query* q, int n, std::vector<NFGUID>& list);
+    int OnlineCount(int scene, int group);
+    bool GroupList(int scene, int group, int who, uint32_t cls_mask, const NFGUID* noSelf, std::vector<NFGUID>& list);
     void DeliverEvents(const nfk_frame_host& f, const NFGUID* ev_self = nullptr, const NFGUID* re_self = nullptr,
                        const uint8_t* ev_same = nullptr);
     uint64_t UsedRows(const NFGUID& self, int rec);

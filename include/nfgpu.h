@@ -453,6 +453,68 @@ int nfk_read_frame(void* world, uint32_t what, nfk_frame_host* out);
 int nfk_rank_top(void* world, int32_t pid, int32_t k, int32_t* n_out, int64_t* guid_head, int64_t* guid_data,
                  double* score);
 
+/* ---- scene queries: NFCKernelModule::GetObjectByProperty (KM:1357-1405), the GetGroupObjectList
+ * overloads (KM:1169-1294), GetSceneOnLineList / GetSceneOnLineCount (KM:1042-1102), GetOnLineCount
+ * (KM:1015).  A batch of n_q <= NFK_MAX_QUERIES queries is answered in one call (more: NFK_ERR_ARG).  A query is a filtered, order-preserving
+ * compaction over the slot range of one scene (NFK_Q_ALL_GROUPS: its groups in group-id order, the
+ * std::map walk of NFCSceneInfo First / Next) or of one scene group:
+ *   who        NFK_Q_PLAYERS: the group's mxPlayerList, NFK_Q_OTHERS: its mxOtherList.  "Players then
+ *              others" (GetGroupObjectList(scene, group, list), KM:1169) is two queries of one batch
+ *   cls_mask   bit c: objects of class c qualify (the classes that have the property, FindProperty
+ *              KM:1365; the strClassName overloads, KM:1231)
+ *   pid        the property compared, or -1: a pure membership list
+ *   mode       NFK_Q_INT_EQ32 (int property): (int64_t)(int32_t)property == value — the reference reads
+ *              the property into an int (KM:1372) and compares it with the argument's NFINT64, so a
+ *              property of 2^32 + 5 matches the argument 5 and a property of 5 does not match 2^32 + 5;
+ *              NFK_Q_OBJ_EQ (object property): both NFGUID halves equal value (data) / value_head (KM:1391)
+ *   skip_obj   an object index left out (noSelf, KM:1270), or -1
+ * The result is owned by the world, in pinned host memory, valid until the next nfk_query_objects /
+ * nfk_execute / nfk_execute_calls: off[n_q + 1], obj[off[n_q]] (object indices, as ev_obj) with query
+ * q's hits at obj[off[q] .. off[q + 1]) in the reference's order — group id ascending, then NFGUID
+ * ascending (NFGUID::operator<) — and exists[n_q]: 0 for a scene (or scene group) that never held an
+ * object of this world (the reference returns false / 0), whose list is empty; a group exists from its
+ * first member on and stays when it is emptied (NFCSceneGroupInfo until ReleaseGroupScene).
+ * An object is a player or an "other" by what nfk_create_objects / nfk_spawn_objects said (its class);
+ * NFCKernelModule::SwitchScene itself moves every object between the groups' PLAYER lists (KM:929, 945
+ * pass bPlayer = true, so an NPC it moves stays listed in its old group): that is not reproduced.
+ * The answer is the reference's NOW: the device state after the last frame (the call waits for the
+ * world's stream like nfk_rank_top, queues nothing and changes nothing a frame reads) with this
+ * window's queued calls on top, by the read-your-writes rule of nfk_get_props — objects whose
+ * membership changed in the window (SwitchScene, DestroyObject, spawn / import) or that have a queued
+ * Set of the queried property are taken out of the device's hits, re-evaluated on the host and merged
+ * back in order.  NFK_ERR_ARG: a bad pid / mode / who, or a mode that does not fit the property's
+ * type; NFK_ERR_STATE before nfk_commit. */
+#define NFK_MAX_QUERIES 4096 /* queries of one nfk_query_objects batch */
+#define NFK_Q_PLAYERS 0
+#define NFK_Q_OTHERS 1
+#define NFK_Q_ALL_GROUPS 1u /* nfk_query::flags: every group of the scene (group is ignored) */
+#define NFK_Q_INT_EQ32 0
+#define NFK_Q_OBJ_EQ 1
+typedef struct nfk_query {
+    int32_t scene, group;
+    uint32_t flags;    /* NFK_Q_ALL_GROUPS */
+    int32_t who;       /* NFK_Q_PLAYERS / NFK_Q_OTHERS */
+    uint32_t cls_mask; /* 16 bits, one per class id */
+    int32_t pid;       /* -1: no property test */
+    int32_t mode;      /* NFK_Q_INT_EQ32 / NFK_Q_OBJ_EQ (with pid >= 0) */
+    int32_t skip_obj;  /* -1: none */
+    int64_t value;      /* the int argument, or the NFGUID's data half (nData64) */
+    int64_t value_head; /* the NFGUID's head half (nHead64) */
+} nfk_query; /* 48 bytes */
+typedef struct nfk_query_result {
+    const uint32_t* off;   /* [n_q + 1] */
+    const int32_t* obj;    /* [off[n_q]] */
+    const uint8_t* exists; /* [n_q] */
+    /* the launches' device time in ms (0 unless nfk_set_profiling is on) and the bytes read back */
+    double kernel_ms;
+    int64_t bytes;
+} nfk_query_result;
+int nfk_query_objects(void* world, int32_t n_q, const nfk_query* q, nfk_query_result* out);
+/* GetSceneOnLineCount(scene) (KM:1083; group < 0) / GetSceneOnLineCount(scene, group) (KM:1090) /
+ * GetOnLineCount (KM:1015; scene < 0: every scene): the players now, from the host's segment
+ * bookkeeping corrected by the window's membership calls — no launch, no device read */
+int nfk_online_count(void* world, int32_t scene, int32_t group, int32_t* n);
+
 /* ---- schema specialisation ----
  * At nfk_commit k_tick is compiled for the world's schema (its heartbeat programs as straight-line
  * code, its working set and event tables as constants) with hipRTC for gfx950, from the same

@@ -12,6 +12,7 @@
 #include <numeric>
 #include <string>
 #include <unordered_map>
+#include <unordered_set>
 #include <vector>
 
 #include <mutex>
@@ -302,6 +303,20 @@ struct World {
     size_t chain_scap = 0;
     char* chain_pin = nullptr;
     size_t chain_pcap = 0;
+    // scene queries (nfk_query_objects): the batch's device scratch (descriptors, tile counts and
+    // bases, offsets and hits) and the pinned host buffer of the uploaded descriptors and the
+    // result, both grown on demand; q_mark[object]: affected in this window (set and cleared per call)
+    void* q_dev = nullptr;
+    size_t q_dcap = 0;
+    char* q_pin = nullptr;
+    size_t q_pcap = 0;
+    std::vector<uint8_t> q_mark;
+    // the scenes and (scene, group) pairs (seg_key_of) whose emptied segment a re-layout dropped: such
+    // a group still exists for the reference (its NFCSceneGroupInfo stays until ReleaseGroupScene).
+    // Written only there, so a world whose groups never empty keeps both sets empty
+    std::unordered_set<uint64_t> known_groups;
+    std::unordered_set<int32_t> known_scenes;
+    hipEvent_t q_ev[2] = {nullptr, nullptr};
 
     bool profiling = false;
     std::vector<PendingTiming> pend;
@@ -1445,7 +1460,12 @@ int plan_membership(World* w, MemPlan& p) {
             const std::pair<int32_t, int32_t> key{old.scene, old.group};
             while (fit != fresh.end() && fit->first < key) push_fresh();
             const bool edited = epos[gi] >= 0;
-            if ((edited ? einfo[epos[gi]].seg.objs : old.objs).empty()) continue;
+            if ((edited ? einfo[epos[gi]].seg.objs : old.objs).empty()) {
+                // (the group stays for the scene queries: NFCSceneGroupInfo until ReleaseGroupScene)
+                w->known_scenes.insert(old.scene);
+                w->known_groups.insert(seg_key_of(old.scene, old.group));
+                continue;
+            }
             World::Seg g;
             g.scene = old.scene;
             g.group = old.group;
@@ -1836,6 +1856,10 @@ int nfk_destroy(void* world) {
     if (w->chain_cnt_d) (void)hipFree(w->chain_cnt_d);
     if (w->chain_scr) (void)hipFree(w->chain_scr);
     if (w->chain_pin) (void)hipHostFree(w->chain_pin);
+    if (w->q_dev) (void)hipFree(w->q_dev);
+    if (w->q_pin) (void)hipHostFree(w->q_pin);
+    for (auto e : w->q_ev)
+        if (e) (void)hipEventDestroy(e);
     for (auto& p : w->pend) {
         (void)hipEventDestroy(p.a);
         (void)hipEventDestroy(p.b);
@@ -2797,22 +2821,16 @@ static int index_queued_sets(World* w) {
     return NFK_OK;
 }
 
-int nfk_get_objects(void* world, int32_t n, const int64_t* gh, const int64_t* gd, const int32_t* pid, int64_t* vh,
-                    int64_t* vd) {
-    World* w = (World*)world;
-    if (!w || n < 0 || (n && (!gh || !gd || !pid || !vh || !vd))) return fail(NFK_ERR_ARG, "null argument");
-    if (!w->committed) return fail(NFK_ERR_STATE, "commit first");
-    std::vector<int32_t> obj(n);
-    if (int rl = find_many_par(w, n, gh, gd, obj.data())) return rl;
+// NFCProperty::GetObject of n (object, object property) pairs as the reference holds them now: the
+// device's value after the last frame, then this window's queued SetObject calls (the last one
+// stays).  Shared by nfk_get_objects and the host side of nfk_query_objects.
+static int current_objects(World* w, int32_t n, const int32_t* obj, const int32_t* pid, int64_t* vh, int64_t* vd) {
     std::vector<uint64_t> src(2 * (size_t)n), got(2 * (size_t)n);
-    for (int32_t i = 0; i < n; i++) {
-        if (obj[i] < 0) return fail(NFK_ERR_NOTFOUND, "There is no object " + std::to_string(gh[i]) + "-" + std::to_string(gd[i]));
-        if (pid[i] < w->n_if || pid[i] >= w->n_prop) return fail(NFK_ERR_ARG, "not an object property");
+    for (int32_t i = 0; i < n; i++)
         for (int h = 0; h < 2; h++) {
             int r = word_src(w, obj[i], pid[i], h, &src[2 * (size_t)i + h]);
             if (r) return r;
         }
-    }
     int r = read_words(w, src, got.data());
     if (r) return r;
     // this window's queued SetObject calls on top: NFCProperty::SetObject keeps the last value
@@ -2828,16 +2846,23 @@ int nfk_get_objects(void* world, int32_t n, const int64_t* gh, const int64_t* gd
     return NFK_OK;
 }
 
-int nfk_get_props(void* world, int32_t n, const int64_t* gh, const int64_t* gd, const int32_t* pid, uint64_t* bits) {
+int nfk_get_objects(void* world, int32_t n, const int64_t* gh, const int64_t* gd, const int32_t* pid, int64_t* vh,
+                    int64_t* vd) {
     World* w = (World*)world;
-    if (!w || n < 0 || (n && (!gh || !gd || !pid || !bits))) return fail(NFK_ERR_ARG, "null argument");
+    if (!w || n < 0 || (n && (!gh || !gd || !pid || !vh || !vd))) return fail(NFK_ERR_ARG, "null argument");
     if (!w->committed) return fail(NFK_ERR_STATE, "commit first");
     std::vector<int32_t> obj(n);
     if (int rl = find_many_par(w, n, gh, gd, obj.data())) return rl;
     for (int32_t i = 0; i < n; i++) {
         if (obj[i] < 0) return fail(NFK_ERR_NOTFOUND, "There is no object " + std::to_string(gh[i]) + "-" + std::to_string(gd[i]));
-        if (pid[i] < 0 || pid[i] >= w->n_if) return fail(NFK_ERR_ARG, "bad property id (object properties: nfk_get_objects)");
+        if (pid[i] < w->n_if || pid[i] >= w->n_prop) return fail(NFK_ERR_ARG, "not an object property");
     }
+    return current_objects(w, n, obj.data(), pid, vh, vd);
+}
+
+// NFCProperty::GetInt / GetFloat of n (object, int / f64 property) pairs as the reference holds them
+// now (raw bits).  Shared by nfk_get_props and the host side of nfk_query_objects.
+static int current_props(World* w, int32_t n, const int32_t* obj, const int32_t* pid, uint64_t* bits) {
     // 1. the world's values after the last frame (a per-window cache of device reads)
     std::vector<uint64_t> src;
     std::vector<int32_t> miss;
@@ -2887,6 +2912,19 @@ int nfk_get_props(void* world, int32_t n, const int64_t* gh, const int64_t* gd, 
         bits[i] = v;
     }
     return NFK_OK;
+}
+
+int nfk_get_props(void* world, int32_t n, const int64_t* gh, const int64_t* gd, const int32_t* pid, uint64_t* bits) {
+    World* w = (World*)world;
+    if (!w || n < 0 || (n && (!gh || !gd || !pid || !bits))) return fail(NFK_ERR_ARG, "null argument");
+    if (!w->committed) return fail(NFK_ERR_STATE, "commit first");
+    std::vector<int32_t> obj(n);
+    if (int rl = find_many_par(w, n, gh, gd, obj.data())) return rl;
+    for (int32_t i = 0; i < n; i++) {
+        if (obj[i] < 0) return fail(NFK_ERR_NOTFOUND, "There is no object " + std::to_string(gh[i]) + "-" + std::to_string(gd[i]));
+        if (pid[i] < 0 || pid[i] >= w->n_if) return fail(NFK_ERR_ARG, "bad property id (object properties: nfk_get_objects)");
+    }
+    return current_props(w, n, obj.data(), pid, bits);
 }
 
 int nfk_exist_schedule(void* world, int64_t gh, int64_t gd, int32_t kind, int32_t* exists) {
@@ -4714,6 +4752,289 @@ int nfk_read_frame(void* world, uint32_t what, nfk_frame_host* o) {
         o->msg_off = (const uint32_t*)(H + o_mo);
         o->msg_rcpt = (const int32_t*)(H + o_mr);
     }
+    return NFK_OK;
+}
+
+// ---- scene queries (nfk_query_objects) ----
+// the segments [s0, s1) of a scene (all: every group, in group-id order) or of one scene group
+static void seg_range(const World* w, int32_t scene, bool all, int32_t group, size_t* s0, size_t* s1) {
+    const uint64_t k0 = seg_key_of(scene, all ? INT32_MIN : group), k1 = seg_key_of(scene, all ? INT32_MAX : group);
+    *s0 = (size_t)(std::lower_bound(w->seg_key.begin(), w->seg_key.end(), k0) - w->seg_key.begin());
+    *s1 = (size_t)(std::upper_bound(w->seg_key.begin(), w->seg_key.end(), k1) - w->seg_key.begin());
+}
+
+static int query_check(const World* w, const nfk_query& q) {
+    if (q.who != NFK_Q_PLAYERS && q.who != NFK_Q_OTHERS) return fail(NFK_ERR_ARG, "nfk_query: bad who");
+    if (q.flags & ~NFK_Q_ALL_GROUPS) return fail(NFK_ERR_ARG, "nfk_query: bad flags");
+    if (q.pid < -1 || q.pid >= w->n_prop) return fail(NFK_ERR_ARG, "nfk_query: bad property id");
+    if (q.pid < 0) return NFK_OK;
+    if (q.mode == NFK_Q_INT_EQ32) {
+        if (q.pid >= w->cfg.n_int) return fail(NFK_ERR_ARG, "nfk_query: NFK_Q_INT_EQ32 on a property that is no int");
+    } else if (q.mode == NFK_Q_OBJ_EQ) {
+        if (q.pid < w->n_if) return fail(NFK_ERR_ARG, "nfk_query: NFK_Q_OBJ_EQ on a property that is no object");
+    } else {
+        return fail(NFK_ERR_ARG, "nfk_query: bad mode");
+    }
+    return NFK_OK;
+}
+
+int nfk_query_objects(void* world, int32_t n_q, const nfk_query* q, nfk_query_result* out) {
+    World* w = (World*)world;
+    if (!w || !out || n_q < 0 || (n_q && !q)) return fail(NFK_ERR_ARG, "null argument");
+    if (!w->committed) return fail(NFK_ERR_STATE, "commit first");
+    if (n_q > NFK_MAX_QUERIES) return fail(NFK_ERR_ARG, "more than NFK_MAX_QUERIES queries in one batch");
+    uint64_t pidmask[2] = {0, 0};
+    for (int32_t i = 0; i < n_q; i++) {
+        if (int r = query_check(w, q[i])) return r;
+        if (q[i].pid >= 0) pidmask[q[i].pid >> 6] |= 1ull << (q[i].pid & 63);
+    }
+    *out = nfk_query_result{};
+    static const uint32_t kNoOff = 0;
+    out->off = &kNoOff;
+    if (n_q == 0) return NFK_OK;
+
+    // the window's affected objects: membership calls (touched), and per queried property the
+    // untouched objects with a queued Set of it, as (pid, object) sorted
+    std::vector<std::pair<int32_t, int32_t>> xaff;
+    if (pidmask[0] | pidmask[1]) {
+        if (int r = index_queued_sets(w)) return r;
+        for (const auto& kv : w->ov_last) {
+            const int32_t pid = (int32_t)(kv.first & 127), o = (int32_t)(kv.first >> 7);
+            if (((pidmask[pid >> 6] >> (pid & 63)) & 1) && !w->m_flag[o]) xaff.push_back({pid, o});
+        }
+        std::sort(xaff.begin(), xaff.end());
+    }
+    auto xaff_of = [&](int32_t pid) {
+        const auto a = std::lower_bound(xaff.begin(), xaff.end(), std::make_pair(pid, INT32_MIN));
+        const auto b = std::lower_bound(xaff.begin(), xaff.end(), std::make_pair(pid + 1, INT32_MIN));
+        return std::make_pair((size_t)(a - xaff.begin()), (size_t)(b - xaff.begin()));
+    };
+
+    // slot ranges, tiles and the bound of each query's hits from the segments' bookkeeping
+    struct Plan { size_t s0, s1; int32_t lo, hi, tiles; size_t ub, n_aff; };
+    std::vector<Plan> pl(n_q);
+    size_t nt = 0, ub = 0, fin = 0;
+    int32_t max_tiles = 0;
+    for (int32_t i = 0; i < n_q; i++) {
+        Plan& p = pl[i];
+        seg_range(w, q[i].scene, (q[i].flags & NFK_Q_ALL_GROUPS) != 0, q[i].group, &p.s0, &p.s1);
+        p.lo = p.hi = 0;
+        p.ub = 0;
+        if (p.s0 < p.s1) {
+            p.lo = w->segs[p.s0].base;
+            p.hi = w->segs[p.s1 - 1].base + (int32_t)w->segs[p.s1 - 1].objs.size();
+            for (size_t g = p.s0; g < p.s1; g++) {
+                const World::Seg& sg = w->segs[g];
+                p.ub += q[i].who == NFK_Q_PLAYERS ? (size_t)sg.np : sg.objs.size() - (size_t)sg.np;
+            }
+            if (p.lo < 0 || p.hi < p.lo || p.hi > w->d.cap) return fail(NFK_ERR_STATE, "segment table out of the slot range");
+        }
+        p.tiles = (p.hi - p.lo + kTile - 1) / kTile;
+        max_tiles = std::max(max_tiles, p.tiles);
+        nt += (size_t)p.tiles;
+        ub += p.ub;
+        p.n_aff = w->touched.size();
+        if (q[i].pid >= 0) {
+            const auto xr = xaff_of(q[i].pid);
+            p.n_aff += xr.second - xr.first;
+        }
+        fin += p.ub + p.n_aff;
+    }
+    const bool correct = !w->touched.empty() || !xaff.empty();
+
+    // one region uploaded (descriptors, first tiles), one region read back (offsets, hits)
+    const size_t nq1 = (size_t)n_q + 1;
+    const size_t u_q = 0, u_t0 = align16((size_t)n_q * sizeof(QDev)), u_end = align16(u_t0 + nq1 * 4);
+    const size_t d_cnt = u_end, d_base = align16(d_cnt + nt * 4), d_off = align16(d_base + (nt + 1) * 4);
+    const size_t r_obj = align16(nq1 * 4), r_bytes = r_obj + ub * 4;  // (within the read-back region)
+    const size_t d_end = d_off + r_bytes;
+    const size_t h_res = u_end, h_foff = align16(h_res + r_bytes), h_fobj = align16(h_foff + nq1 * 4);
+    const size_t h_ex = align16(h_fobj + (correct ? fin : 0) * 4), h_end = h_ex + align16((size_t)n_q);
+    if (int r = dev_reserve(w, &w->q_dev, &w->q_dcap, d_end)) return r;
+    if (h_end > w->q_pcap) {
+        if (w->q_pin) HIPCHK(hipHostFree(w->q_pin));
+        w->q_pin = nullptr;
+        const size_t c = std::max(h_end, w->q_pcap + w->q_pcap / 2);
+        w->q_pcap = 0;  // (until the new buffer exists)
+        HIPCHK(hipHostMalloc((void**)&w->q_pin, c, hipHostMallocDefault));
+        w->q_pcap = c;
+    }
+    char* H = w->q_pin;
+    char* D = (char*)w->q_dev;
+    QDev* hq = (QDev*)(H + u_q);
+    int32_t* ht0 = (int32_t*)(H + u_t0);
+    uint8_t* exists = (uint8_t*)(H + h_ex);
+    int32_t t0 = 0;
+    for (int32_t i = 0; i < n_q; i++) {
+        const Plan& p = pl[i];
+        QDev x{};
+        x.lo = p.lo;
+        x.hi = p.hi;
+        x.tile0 = ht0[i] = t0;
+        t0 += p.tiles;
+        x.who = q[i].who;
+        x.cls_mask = q[i].cls_mask & 0x7FFFu;  // (class 15 marks a free slot)
+        x.mode = q[i].pid < 0 ? -1 : q[i].mode;
+        x.skip_slot = -1;
+        const int32_t so = q[i].skip_obj;
+        if (so >= 0 && so < w->n_obj && !w->m_flag[so]) x.skip_slot = w->slot_of_obj[so];
+        if (q[i].pid >= 0) {
+            x.p_off = w->tab.p_off[q[i].pid];
+            x.p_str = w->tab.p_str[q[i].pid];
+        }
+        x.value = (uint64_t)q[i].value;
+        x.value_head = (uint64_t)q[i].value_head;
+        hq[i] = x;
+        // it has a segment, or had one (an object of the window entering it: below)
+        exists[i] = p.s0 < p.s1 || ((q[i].flags & NFK_Q_ALL_GROUPS)
+                                        ? w->known_scenes.count(q[i].scene)
+                                        : w->known_groups.count(seg_key_of(q[i].scene, q[i].group)))
+                        ? 1
+                        : 0;
+    }
+    ht0[n_q] = t0;
+    uint32_t* roff = (uint32_t*)(H + h_res);
+    int32_t* robj = (int32_t*)(H + h_res + r_obj);
+    if (nt == 0) {
+        memset(roff, 0, nq1 * 4);  // (no slot to look at: nothing is launched)
+    } else {
+        const bool timed = w->profiling;
+        if (timed)
+            for (auto& e : w->q_ev)
+                if (!e) HIPCHK(hipEventCreate(&e));
+        HIPCHK(hipMemcpyAsync(D, H, u_end, hipMemcpyHostToDevice, w->stream));
+        if (timed) HIPCHK(hipEventRecord(w->q_ev[0], w->stream));
+        const dim3 grid((unsigned)max_tiles, (unsigned)n_q);
+        hipLaunchKernelGGL(k_query<false>, grid, dim3(kTPB), 0, w->stream, (const QDev*)(D + u_q), w->d.fan_desc,
+                           (const uint64_t*)w->d.pmem, (const int32_t*)w->slot_obj_d, (uint32_t*)(D + d_cnt),
+                           (const uint32_t*)nullptr, (int32_t*)nullptr, 0u);
+        hipLaunchKernelGGL(k_query_scan, dim3(1), dim3(1024), 0, w->stream, (const uint32_t*)(D + d_cnt),
+                           (uint32_t*)(D + d_base), (int)nt, (const int32_t*)(D + u_t0), (int)n_q, (uint32_t*)(D + d_off));
+        hipLaunchKernelGGL(k_query<true>, grid, dim3(kTPB), 0, w->stream, (const QDev*)(D + u_q), w->d.fan_desc,
+                           (const uint64_t*)w->d.pmem, (const int32_t*)w->slot_obj_d, (uint32_t*)nullptr,
+                           (const uint32_t*)(D + d_base), (int32_t*)(D + d_off + r_obj), (uint32_t)ub);
+        HIPCHK(hipGetLastError());
+        if (timed) HIPCHK(hipEventRecord(w->q_ev[1], w->stream));
+        HIPCHK(hipMemcpyAsync(H + h_res, D + d_off, r_bytes, hipMemcpyDeviceToHost, w->stream));
+        HIPCHK(hipStreamSynchronize(w->stream));
+        out->bytes = (int64_t)r_bytes;
+        if (timed) {
+            float ms = 0;
+            HIPCHK(hipEventElapsedTime(&ms, w->q_ev[0], w->q_ev[1]));
+            out->kernel_ms = ms;
+        }
+        if (roff[n_q] > ub) return fail(NFK_ERR_DEVICE, "scene query: more hits than the segments' members");
+    }
+    out->exists = exists;
+    out->off = roff;
+    out->obj = robj;
+    if (!correct) return NFK_OK;
+
+    // the window's calls on top: every affected object is evaluated on the host, from the membership
+    // arrays as the calls have left them and its property as nfk_get_props / nfk_get_objects read it
+    struct Cand { int32_t q, o; };
+    std::vector<Cand> cand;                 // membership passed (in query order)
+    std::vector<int32_t> ro, rp, rc;        // reads of int properties: object, pid, candidate
+    std::vector<int32_t> oo, op, oc;        // ... of object properties
+    for (int32_t i = 0; i < n_q; i++) {
+        const bool all = (q[i].flags & NFK_Q_ALL_GROUPS) != 0;
+        auto eval = [&](int32_t o) {
+            if (!w->alive[o] || w->scene[o] != q[i].scene || (!all && w->group[o] != q[i].group)) return;
+            if (w->m_flag[o]) exists[i] = 1;  // (a scene group the window's calls bring into being)
+            if ((w->isplayer[o] != 0) != (q[i].who == NFK_Q_PLAYERS) || !((q[i].cls_mask >> w->cls[o]) & 1u) ||
+                o == q[i].skip_obj)
+                return;
+            if (q[i].pid >= 0) {
+                auto& xo = q[i].mode == NFK_Q_OBJ_EQ ? oo : ro;
+                auto& xp = q[i].mode == NFK_Q_OBJ_EQ ? op : rp;
+                auto& xc = q[i].mode == NFK_Q_OBJ_EQ ? oc : rc;
+                xo.push_back(o);
+                xp.push_back(q[i].pid);
+                xc.push_back((int32_t)cand.size());
+            }
+            cand.push_back({i, o});
+        };
+        for (int32_t o : w->touched) eval(o);
+        if (q[i].pid >= 0) {
+            const auto xr = xaff_of(q[i].pid);
+            for (size_t j = xr.first; j < xr.second; j++) eval(xaff[j].second);
+        }
+    }
+    std::vector<uint8_t> keep(cand.size(), 1);
+    if (!ro.empty()) {
+        std::vector<uint64_t> bits(ro.size());
+        if (int r = current_props(w, (int32_t)ro.size(), ro.data(), rp.data(), bits.data())) return r;
+        for (size_t j = 0; j < ro.size(); j++)
+            keep[rc[j]] = (int64_t)(int32_t)(uint32_t)bits[j] == q[cand[rc[j]].q].value;
+    }
+    if (!oo.empty()) {
+        std::vector<int64_t> vh(oo.size()), vd(oo.size());
+        if (int r = current_objects(w, (int32_t)oo.size(), oo.data(), op.data(), vh.data(), vd.data())) return r;
+        for (size_t j = 0; j < oo.size(); j++) {
+            const nfk_query& qq = q[cand[oc[j]].q];
+            keep[oc[j]] = vd[j] == qq.value && vh[j] == qq.value_head;
+        }
+    }
+    // each list without its affected objects, the re-evaluated ones merged in by (group, NFGUID)
+    auto before = [&](int32_t a, int32_t b) { return w->group[a] != w->group[b] ? w->group[a] < w->group[b] : guid_less(w, a, b); };
+    if (w->q_mark.size() < (size_t)w->n_obj) w->q_mark.resize(w->n_obj, 0);
+    for (int32_t o : w->touched) w->q_mark[o] = 1;
+    uint32_t* foff = (uint32_t*)(H + h_foff);
+    int32_t* fobj = (int32_t*)(H + h_fobj);
+    std::vector<int32_t> add;
+    size_t c0 = 0;
+    uint32_t at = 0;
+    for (int32_t i = 0; i < n_q; i++) {
+        foff[i] = at;
+        add.clear();
+        for (; c0 < cand.size() && cand[c0].q == i; c0++)
+            if (keep[c0]) add.push_back(cand[c0].o);
+        std::sort(add.begin(), add.end(), before);
+        std::pair<size_t, size_t> xr{0, 0};
+        if (q[i].pid >= 0) xr = xaff_of(q[i].pid);
+        for (size_t j = xr.first; j < xr.second; j++) w->q_mark[xaff[j].second] = 1;
+        size_t a = 0;
+        for (uint32_t h = roff[i]; h < roff[i + 1]; h++) {
+            const int32_t o = robj[h];
+            if (w->q_mark[o]) continue;
+            while (a < add.size() && before(add[a], o)) fobj[at++] = add[a++];
+            fobj[at++] = o;
+        }
+        while (a < add.size()) fobj[at++] = add[a++];
+        for (size_t j = xr.first; j < xr.second; j++) w->q_mark[xaff[j].second] = 0;
+    }
+    foff[n_q] = at;
+    for (int32_t o : w->touched) w->q_mark[o] = 0;
+    out->off = foff;
+    out->obj = fobj;
+    return NFK_OK;
+}
+
+int nfk_online_count(void* world, int32_t scene, int32_t group, int32_t* n) {
+    World* w = (World*)world;
+    if (!w || !n) return fail(NFK_ERR_ARG, "null argument");
+    if (!w->committed) return fail(NFK_ERR_STATE, "commit first");
+    size_t s0 = 0, s1 = w->segs.size();
+    if (scene >= 0) seg_range(w, scene, group < 0, group, &s0, &s1);
+    int64_t c = 0;
+    for (size_t g = s0; g < s1; g++) c += w->segs[g].np;
+    // the window's membership calls: a touched player leaves the segment of its slot and, alive,
+    // joins the scene group the calls have left it in
+    for (int32_t o : w->touched) {
+        if (!w->isplayer[o]) continue;
+        const int32_t sl = w->slot_of_obj[o];
+        if (sl >= 0 && w->src_row[o] < 0) {
+            size_t a = 0, b = w->segs.size();  // the last segment whose base is <= sl
+            while (b - a > 1) {
+                const size_t m = (a + b) / 2;
+                if (w->segs[m].base <= sl) a = m;
+                else b = m;
+            }
+            if (a >= s0 && a < s1) c--;
+        }
+        if (w->alive[o] && (scene < 0 || (w->scene[o] == scene && (group < 0 || w->group[o] == group)))) c++;
+    }
+    *n = (int32_t)c;
     return NFK_OK;
 }
 

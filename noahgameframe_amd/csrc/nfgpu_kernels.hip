@@ -2286,4 +2286,89 @@ __global__ __launch_bounds__(kTPB) void k_permute3(const uint32_t* __restrict__ 
     co[i] = c[j];
 }
 
+// ---------------------------------------------------------------------------------
+// Scene queries (nfk_query_objects): a filtered, order-preserving compaction over one contiguous
+// slot range per query.  Slots are sorted by (scene, group, NFGUID), so a hit's place in its
+// query's list is the count of hits at lower slots — taken from POSITION alone: k_query<false>
+// counts each 256-slot tile's hits, k_query_scan scans the batch's tile counts (one workgroup),
+// k_query<true> evaluates the predicate again and writes slot_obj[slot] at base[tile] + rank in
+// tile.  No atomic decides a place and no workgroup waits on another.
+struct QDev {
+    int32_t lo, hi;     // slot range [lo, hi): slack slots inside carry class 15
+    int32_t tile0;      // its first tile in the batch's count / base arrays (tile t = slots lo + 256 t ...)
+    int32_t who;        // NFK_Q_PLAYERS / NFK_Q_OTHERS
+    uint32_t cls_mask;
+    int32_t mode;       // NFK_Q_INT_EQ32 / NFK_Q_OBJ_EQ, -1: no property test
+    int32_t skip_slot;  // -1: none
+    int32_t p_str;      // the property's column (Tables::p_off / p_str)
+    int64_t p_off;
+    uint64_t value, value_head;
+};
+__device__ __forceinline__ bool query_hit(const QDev& q, const uint64_t* __restrict__ fan_desc,
+                                          const uint64_t* __restrict__ pmem, int slot) {
+    if (slot >= q.hi) return false;
+    const uint64_t desc = fan_desc[slot];
+    const uint32_t cls = (uint32_t)(desc >> 60);
+    if (cls == 0xF || !((q.cls_mask >> cls) & 1u)) return false;
+    const bool player = ((desc >> 46) & 0x3FFF) != 0;
+    if (player != (q.who == NFK_Q_PLAYERS) || slot == q.skip_slot) return false;
+    if (q.mode < 0) return true;
+    // the property word only of the slots that passed the membership test
+    const uint64_t* p = pmem + q.p_off + (int64_t)slot * q.p_str;
+    if (q.mode == NFK_Q_INT_EQ32) return (uint64_t)(int64_t)(int32_t)(uint32_t)p[0] == q.value;
+    return p[0] == q.value && p[1] == q.value_head;  // (data, head)
+}
+template <bool kWrite>
+__global__ __launch_bounds__(kTPB) void k_query(const QDev* __restrict__ qs, const uint64_t* __restrict__ fan_desc,
+                                                const uint64_t* __restrict__ pmem,
+                                                const int32_t* __restrict__ slot_obj, uint32_t* __restrict__ cnt,
+                                                const uint32_t* __restrict__ base, int32_t* __restrict__ out,
+                                                uint32_t out_cap) {
+    __shared__ uint32_t s_w[kTPB / 64];
+    const QDev q = qs[blockIdx.y];
+    const int64_t s0 = (int64_t)q.lo + (int64_t)blockIdx.x * kTile;
+    if (s0 >= q.hi) return;  // (uniform: the grid's x is the batch's longest range)
+    const int slot = (int)s0 + (int)threadIdx.x;
+    const bool hit = query_hit(q, fan_desc, pmem, slot);
+    const unsigned long long b = __ballot(hit);
+    const int w = threadIdx.x >> 6;
+    if ((threadIdx.x & 63) == 0) s_w[w] = (uint32_t)__builtin_popcountll(b);
+    __syncthreads();
+    if constexpr (!kWrite) {
+        if (threadIdx.x == 0) cnt[q.tile0 + (int)blockIdx.x] = s_w[0] + s_w[1] + s_w[2] + s_w[3];
+    } else {
+        uint32_t r = base[q.tile0 + (int)blockIdx.x] +
+                     __builtin_amdgcn_mbcnt_hi((uint32_t)(b >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)b, 0u));
+        for (int i = 0; i < w; i++) r += s_w[i];
+        // (out_cap: the host's bound of the batch's hits; the host checks the total against it)
+        if (hit && r < out_cap) out[r] = slot_obj[slot];
+    }
+}
+// k_scan_counts over the batch's n tile counts, and the queries' offsets off[q] = base[tile0[q]]
+// (tile0[n_q] = n) beside the hits, so one copy brings both back
+__global__ __launch_bounds__(1024) void k_query_scan(const uint32_t* __restrict__ cnt, uint32_t* __restrict__ out, int n,
+                                                     const int32_t* __restrict__ tile0, int n_q,
+                                                     uint32_t* __restrict__ off) {
+    __shared__ uint32_t s[1024];
+    const int per = (n + 1023) / 1024, i0 = min(n, (int)threadIdx.x * per), i1 = min(n, i0 + per);
+    uint32_t sum = 0;
+    for (int i = i0; i < i1; i++) sum += cnt[i];
+    s[threadIdx.x] = sum;
+    __syncthreads();
+    for (int o = 1; o < 1024; o <<= 1) {
+        const uint32_t v = threadIdx.x >= (unsigned)o ? s[threadIdx.x - o] : 0u;
+        __syncthreads();
+        s[threadIdx.x] += v;
+        __syncthreads();
+    }
+    uint32_t acc = s[threadIdx.x] - sum;
+    for (int i = i0; i < i1; i++) {
+        out[i] = acc;
+        acc += cnt[i];
+    }
+    if (threadIdx.x == 1023) out[n] = s[1023];
+    __syncthreads();  // (out: this workgroup's own global stores)
+    for (int q = threadIdx.x; q <= n_q; q += 1024) off[q] = out[tile0[q]];
+}
+
 }  // namespace nfgpu

@@ -1,6 +1,8 @@
 // NFGPUKernelModule.cpp — host plugin over the C-ABI (see include/NFGPUKernelModule.hpp).
 #include "NFGPUKernelModule.hpp"
 
+#include <dlfcn.h>
+
 #include <algorithm>
 #include <chrono>
 #include <cstdlib>
@@ -552,6 +554,124 @@ bool NFGPUKernelModule::GetRange(const std::string& prop, int k,
         memberScoreVec.emplace_back(std::to_string(gh[i]) + "-" + std::to_string(gd[i]), sc[i]);
     return true;
 }
+
+// ---- scene queries (KM:1015-1102, 1169-1294, 1357-1405) ----
+// nfk_query_objects / nfk_online_count are looked up at first use, so this library still loads and
+// links over an nfgpu library that predates them (the C-ABI test double); there the queries fail
+// like any other C-ABI call.
+// RTLD_DEFAULT sees the global scope only; a host that loaded this library (and with it libnfgpu.so)
+// RTLD_LOCAL — ctypes.CDLL, a plugin loader's dlopen — finds the entry point through the handle of the
+// already loaded libnfgpu.so (RTLD_NOLOAD: nothing new is loaded).
+static void* nfgpu_symbol(const char* name) {
+    if (void* p = dlsym(RTLD_DEFAULT, name)) return p;
+    if (void* h = dlopen("libnfgpu.so", RTLD_NOLOAD | RTLD_LAZY)) return dlsym(h, name);
+    return nullptr;
+}
+
+bool NFGPUKernelModule::RunQueries(const nfk_query* q, int n, std::vector<NFGUID>& list) {
+    using Fn = int (*)(void*, int32_t, const nfk_query*, nfk_query_result*);
+    static const Fn fn = (Fn)nfgpu_symbol("nfk_query_objects");
+    if (!fn) throw std::runtime_error("nfk_query_objects: the nfgpu library has no such entry point");
+    Flush();  // (the buffered Set and schedule calls first: they are visible to the query)
+    nfk_query_result r{};
+    check(fn(world_, n, q, &r), "nfk_query_objects");
+    const uint32_t tot = r.off[n];
+    list.reserve(list.size() + tot);
+    for (uint32_t i = 0; i < tot; i++) list.push_back(guids_[(size_t)r.obj[i]]);
+    return n > 0 && r.exists[0] != 0;
+}
+
+int NFGPUKernelModule::OnlineCount(int scene, int group) {
+    using Fn = int (*)(void*, int32_t, int32_t, int32_t*);
+    static const Fn fn = (Fn)nfgpu_symbol("nfk_online_count");
+    if (!fn) throw std::runtime_error("nfk_online_count: the nfgpu library has no such entry point");
+    if (!committed_) return 0;
+    Flush();
+    int32_t n = 0;
+    check(fn(world_, scene, group, &n), "nfk_online_count");
+    return n;
+}
+
+int NFGPUKernelModule::GetObjectByProperty(int nSceneID, const std::string& name, const TData& valueArg,
+                                           std::vector<NFGUID>& list) {
+    const int p = prop_ix_.find(name);
+    if (!committed_ || p < 0) return (int)list.size();  // FindProperty fails for every object (KM:1365)
+    const TDATA_TYPE pt = props_[(size_t)p].type, at = valueArg.GetType();
+    if (at != TDATA_INT && at != TDATA_OBJECT) return (int)list.size();  // `default:` (KM:1398)
+    nfk_query q{};
+    q.scene = nSceneID;
+    q.flags = NFK_Q_ALL_GROUPS;
+    q.who = NFK_Q_PLAYERS;
+    q.skip_obj = -1;
+    bool named = false;  // the classes that have the property
+    for (size_t c = 0; c < classes_.size(); c++)
+        if (classes_[c].prop_flags.count(name)) {
+            q.cls_mask |= 1u << c;
+            named = true;
+        }
+    if (!named) q.cls_mask = 0x7FFFu;
+    q.pid = -1;
+    if (at == pt) {
+        q.pid = dev_pid_[(size_t)p];
+        q.mode = at == TDATA_INT ? NFK_Q_INT_EQ32 : NFK_Q_OBJ_EQ;
+        q.value = at == TDATA_INT ? valueArg.i : valueArg.o.nData64;
+        q.value_head = at == TDATA_INT ? 0 : valueArg.o.nHead64;
+    } else if (at == TDATA_INT ? valueArg.i != 0 : !valueArg.o.IsNull()) {
+        return (int)list.size();  // the getter of the argument's type reads the null value
+    }
+    RunQueries(&q, 1, list);
+    return (int)list.size();
+}
+
+bool NFGPUKernelModule::GroupList(int scene, int group, int who, uint32_t cls_mask, const NFGUID* noSelf,
+                                  std::vector<NFGUID>& list) {
+    if (!committed_) return false;
+    nfk_query q[2] = {};
+    const int n = who < 0 ? 2 : 1;  // players then others (KM:1169)
+    for (int i = 0; i < n; i++) {
+        q[i].scene = scene;
+        q[i].group = group;
+        q[i].who = who < 0 ? (i == 0 ? NFK_Q_PLAYERS : NFK_Q_OTHERS) : who;
+        q[i].cls_mask = cls_mask;
+        q[i].pid = -1;
+        q[i].skip_obj = noSelf ? ObjectIndex(*noSelf) : -1;
+    }
+    return RunQueries(q, n, list);
+}
+
+bool NFGPUKernelModule::GetGroupObjectList(int nSceneID, int nGroupID, std::vector<NFGUID>& list) {
+    return GroupList(nSceneID, nGroupID, -1, 0x7FFFu, nullptr, list);
+}
+bool NFGPUKernelModule::GetGroupObjectList(int nSceneID, int nGroupID, std::vector<NFGUID>& list, bool bPlayer) {
+    return GroupList(nSceneID, nGroupID, bPlayer ? NFK_Q_PLAYERS : NFK_Q_OTHERS, 0x7FFFu, nullptr, list);
+}
+bool NFGPUKernelModule::GetGroupObjectList(int nSceneID, int nGroupID, const std::string& strClassName,
+                                           std::vector<NFGUID>& list) {
+    auto c = class_id_.find(strClassName);
+    return GroupList(nSceneID, nGroupID, -1, c == class_id_.end() ? 0u : 1u << c->second, nullptr, list);
+}
+bool NFGPUKernelModule::GetGroupObjectList(int nSceneID, int nGroupID, const std::string& strClassName,
+                                           const NFGUID& noSelf, std::vector<NFGUID>& list) {
+    auto c = class_id_.find(strClassName);
+    return GroupList(nSceneID, nGroupID, -1, c == class_id_.end() ? 0u : 1u << c->second, &noSelf, list);
+}
+
+int NFGPUKernelModule::GetSceneOnLineList(int nSceneID, std::vector<NFGUID>& list) {
+    if (!committed_) return (int)list.size();
+    nfk_query q{};
+    q.scene = nSceneID;
+    q.flags = NFK_Q_ALL_GROUPS;
+    q.who = NFK_Q_PLAYERS;
+    q.cls_mask = 0x7FFFu;
+    q.pid = q.skip_obj = -1;
+    RunQueries(&q, 1, list);
+    return (int)list.size();
+}
+int NFGPUKernelModule::GetSceneOnLineCount(int nSceneID) { return nSceneID < 0 ? 0 : OnlineCount(nSceneID, -1); }
+int NFGPUKernelModule::GetSceneOnLineCount(int nSceneID, int nGroupID) {
+    return nSceneID < 0 || nGroupID < 0 ? 0 : OnlineCount(nSceneID, nGroupID);
+}
+int NFGPUKernelModule::GetOnLineCount() { return OnlineCount(-1, -1); }
 
 int NFGPUKernelModule::ObjectIndex(const NFGUID& g) const { return obj_of_.find(g.nHead64, g.nData64); }
 

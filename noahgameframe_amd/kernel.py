@@ -56,6 +56,32 @@ class Outputs(ctypes.Structure):
                   "msg_rcpt", "slot_obj", "ev_old_h", "ev_new_h"]])
 
 
+class Query(ctypes.Structure):
+    """nfk_query (include/nfgpu.h): one scene query of a nfk_query_objects batch."""
+    _fields_ = [("scene", ctypes.c_int32), ("group", ctypes.c_int32), ("flags", ctypes.c_uint32),
+                ("who", ctypes.c_int32), ("cls_mask", ctypes.c_uint32), ("pid", ctypes.c_int32),
+                ("mode", ctypes.c_int32), ("skip_obj", ctypes.c_int32), ("value", ctypes.c_int64),
+                ("value_head", ctypes.c_int64)]
+
+
+class QueryResult(ctypes.Structure):
+    _fields_ = [("off", ctypes.POINTER(ctypes.c_uint32)), ("obj", ctypes.POINTER(ctypes.c_int32)),
+                ("exists", ctypes.POINTER(ctypes.c_uint8)), ("kernel_ms", ctypes.c_double),
+                ("bytes", ctypes.c_int64)]
+
+
+Q_PLAYERS, Q_OTHERS = 0, 1
+Q_ALL_GROUPS = 1
+Q_INT_EQ32, Q_OBJ_EQ = 0, 1
+
+
+def query(scene, group=None, who=Q_PLAYERS, cls_mask=0x7FFF, pid=-1, mode=Q_INT_EQ32, value=0, value_head=0,
+          skip_obj=-1):
+    """One nfk_query; group None = every group of the scene, in group-id order."""
+    return Query(int(scene), 0 if group is None else int(group), Q_ALL_GROUPS if group is None else 0, int(who),
+                 int(cls_mask), int(pid), int(mode), int(skip_obj), int(value), int(value_head))
+
+
 N_KERNEL_TIMERS = 7
 KERNEL_TIMER_NAMES = ["k_tick", "k_records", "k_fanout", "aux", "k_scan_tiles", "membership", "k_chain"]
 
@@ -103,6 +129,7 @@ def load_library(path=LIB_PATH):
         "nfk_load_object": [VP, I32, VP, VP], "nfk_set_objects": [VP, I32, VP, VP, VP, VP, VP],
         "nfk_get_objects": [VP, I32, VP, VP, VP, VP, VP], "nfk_read_object": [VP, I32, VP, VP],
         "nfk_read_events_obj": [VP, VP, VP], "nfk_record_rows": [VP, I32, VP, VP, VP, VP, VP, VP],
+        "nfk_query_objects": [VP, I32, VP, P(QueryResult)], "nfk_online_count": [VP, I32, I32, VP],
     }
     for name, args in sig.items():
         if not hasattr(lib, name) and os.environ.get("NFGPU_LIB"):
@@ -398,6 +425,89 @@ class NFKernelModule:
         n = ctypes.c_int32()
         self._chk(self.lib.nfk_rank_top(self.h, pid, int(k), ctypes.byref(n), _p(gh), _p(gd), _p(sc)))
         return gh[:n.value], gd[:n.value], sc[:n.value]
+
+    # ---- scene queries (NFCKernelModule::GetObjectByProperty / GetGroupObjectList, KM:1169-1405) ----
+    def query_objects(self, queries, with_exists=False, stats=None):
+        """nfk_query_objects: one batch of `query(...)` records -> a list of object-index arrays (the
+        outputs' ev_obj indices) in the reference's order: group id, then NFGUID.  with_exists: also
+        the per-query exists flags (False: this world holds no such scene / scene group).  stats: a
+        dict that receives the launches' device time (kernel_ms, with set_profiling(True)) and the
+        bytes read back."""
+        qs = (Query * max(len(queries), 1))(*queries)
+        res = QueryResult()
+        self._chk(self.lib.nfk_query_objects(self.h, len(queries), qs, ctypes.byref(res)))
+        n = len(queries)
+        off = np.ctypeslib.as_array(res.off, (n + 1,)).copy() if n else np.zeros(1, np.uint32)
+        tot = int(off[n])
+        obj = np.ctypeslib.as_array(res.obj, (tot,)).copy() if tot else np.zeros(0, np.int32)
+        out = [obj[int(off[i]):int(off[i + 1])] for i in range(n)]
+        if stats is not None:
+            stats["kernel_ms"], stats["bytes"] = res.kernel_ms, res.bytes
+        if with_exists:
+            ex = np.ctypeslib.as_array(res.exists, (n,)).astype(bool) if n else np.zeros(0, bool)
+            return out, ex
+        return out
+
+    def _guids(self, obj, guid_head, guid_data):
+        return [(int(guid_head[o]), int(guid_data[o])) for o in obj]
+
+    def object_by_property(self, scene, prop, value):
+        """NFCKernelModule::GetObjectByProperty (KM:1357-1405) over the scene's players, as object
+        indices: `value` an int (compared as the reference does, through an int: KM:1372), a
+        (head, data) NFGUID pair, or a float (matches nothing, KM:1398).  An argument of another type
+        than the property reads the getter's null value (TData::GetInt 0 / GetObject the null NFGUID).
+        Every class is taken to have the property (cls_mask 0x7FFF: this mirror keeps no per-class
+        property list, and a workload's classes share one schema); the C++ plugin builds the mask
+        from SetPropertyFlags.  A caller with classes that lack it passes its own mask to query()."""
+        pid = wl.PID[prop] if isinstance(prop, str) else int(prop)
+        n_if = self.n_int + self.n_flt
+        if isinstance(value, float):
+            return np.zeros(0, np.int32)
+        is_obj = isinstance(value, tuple)
+        if is_obj and pid >= n_if:
+            q = query(scene, pid=pid, mode=Q_OBJ_EQ, value=value[1], value_head=value[0])
+        elif not is_obj and pid < self.n_int:
+            q = query(scene, pid=pid, mode=Q_INT_EQ32, value=value)
+        else:   # the getter of the argument's type reads the null value from the property
+            null = (tuple(value) == (0, 0)) if is_obj else (int(value) == 0)
+            if not null:
+                return np.zeros(0, np.int32)
+            q = query(scene)
+        return self.query_objects([q])[0]
+
+    def group_object_list(self, scene, group, who=None, no_self=-1, cls=None):
+        """NFCKernelModule::GetGroupObjectList (KM:1169-1294) as (found, object indices): who = True
+        the group's players, False its other objects, None players then others (KM:1169); no_self: an
+        object index left out (KM:1270); cls: only objects of that class id (the strClassName
+        overloads)."""
+        mask = 0x7FFF if cls is None else 1 << int(cls)
+        whos = [Q_PLAYERS, Q_OTHERS] if who is None else [Q_PLAYERS if who else Q_OTHERS]
+        lists, ex = self.query_objects([query(scene, group, w, mask, skip_obj=no_self) for w in whos], with_exists=True)
+        return bool(ex[0]), np.concatenate(lists)
+
+    def GetObjectByProperty(self, scene, prop, value, guid_head, guid_data):
+        """object_by_property as NFGUIDs (head, data); guid_head / guid_data: the NFGUIDs by object
+        index, which the caller holds"""
+        return self._guids(self.object_by_property(scene, prop, value), guid_head, guid_data)
+
+    def GetGroupObjectList(self, scene, group, who, guid_head, guid_data, no_self=-1, cls=None):
+        """group_object_list's list as NFGUIDs (head, data)"""
+        return self._guids(self.group_object_list(scene, group, who, no_self, cls)[1], guid_head, guid_data)
+
+    def GetSceneOnLineList(self, scene, guid_head, guid_data):
+        """NFCKernelModule::GetSceneOnLineList (KM:1042): the players of every group of the scene"""
+        return self._guids(self.query_objects([query(scene)])[0], guid_head, guid_data)
+
+    def online_count(self, scene=-1, group=-1):
+        n = ctypes.c_int32()
+        self._chk(self.lib.nfk_online_count(self.h, int(scene), int(group), ctypes.byref(n)))
+        return n.value
+
+    def GetSceneOnLineCount(self, scene, group=-1):
+        return self.online_count(scene, group)
+
+    def GetOnLineCount(self):
+        return self.online_count()
 
     # ---- one frame ----
     def Execute(self, now_ms):
