@@ -409,6 +409,31 @@ public:
     // like GetProperty*; 0 for an unused row (NFCRecord::GetInt, RC:623)
     int64_t GetRecordInt(const NFGUID& self, const std::string& strRecordName, int nRow, int nCol);
     double GetRecordFloat(const NFGUID& self, const std::string& strRecordName, int nRow, int nCol);
+    // NFCRecord::FindInt / FindFloat / FindRowByColValue / QueryRow (RC:778-910, RC:554) through the
+    // record of `self`, NFIDataList as std::vector: one device find each (nfk_find_rows), after a
+    // Flush() like the other record calls, so the answer is the reference's now.  Exactly the
+    // reference's results: -1, with nothing appended, for an unknown object or record, an invalid
+    // column or a column of another type than the call's; else the rows whose used cell equals the
+    // value (ints by 64-bit equality, floats by ==) are APPENDED to varResult in ascending order
+    // and the return value is varResult's total size (RC:856), not this call's hits.  A removed
+    // row's stale cell is not found.  FindRowByColValue tests var's element 0 against the column's
+    // type and then reads the value at index nCol of var, not 0 (RC:794): 0 / 0.0 when var is
+    // shorter or that element has another type (NFCDataList::Int).  QueryRow clears varList, then
+    // returns the row's cells (one nfk_get_records of cols cells); false, varList untouched, for an
+    // invalid or unused row.  They throw std::runtime_error when the nfgpu library loaded has no
+    // nfk_find_rows, as every failed C-ABI call does.
+    int FindInt(const NFGUID& self, const std::string& strRecordName, int nCol, int64_t value, std::vector<int>& varResult);
+    int FindFloat(const NFGUID& self, const std::string& strRecordName, int nCol, double value,
+                  std::vector<int>& varResult);
+    int FindRowByColValue(const NFGUID& self, const std::string& strRecordName, int nCol, const std::vector<TData>& var,
+                          std::vector<int>& varResult);
+    bool QueryRow(const NFGUID& self, const std::string& strRecordName, int nRow, std::vector<TData>& varList);
+    // a frame-level batch of finds in one nfk_find_rows call: one (object, record, column, value)
+    // per entry, value.GetType() the find's type; hits[i].mask bit r: row r is a hit;
+    // hits[i].invalid where the single call would return -1 (its mask is then 0)
+    struct RowFind { NFGUID self; std::string strRecordName; int nCol = 0; TData value; };
+    struct RowHits { uint64_t mask = 0; bool invalid = false; };
+    void FindRows(const std::vector<RowFind>& finds, std::vector<RowHits>& hits);
     // NFCKernelModule::SwitchScene (KM:901-951); writes SceneID/GroupID/X/Y/Z when the schema has
     // them; like the reference, fOrient and arg are not used
     bool SwitchScene(const NFGUID& self, int nTargetSceneID, int nTargetGroupID, float fX, float fY, float fZ,

@@ -515,6 +515,34 @@ int nfk_query_objects(void* world, int32_t n_q, const nfk_query* q, nfk_query_re
  * bookkeeping corrected by the window's membership calls — no launch, no device read */
 int nfk_online_count(void* world, int32_t scene, int32_t group, int32_t* n);
 
+/* ---- record finds: NFCRecord::FindInt / FindFloat / FindRowByColValue (RC:778-910) ----
+ * n (object, record, column, argument) finds answered in one call: masks[i] has bit r set when row
+ * r of the record is used and its cell in column col[i] equals bits[i] under the column's type —
+ * an int column by 64-bit equality (RC:850; 5 does not match 2^32 + 5, unlike NFK_Q_INT_EQ32), an
+ * f64 column by the C == on doubles (RC:892: -0.0 finds 0.0, a NaN cell is never found, not by a
+ * NaN argument either).  The reference's list (rows ascending) and count follow from the bits; a
+ * Remove leaves a cell's value behind (RC:1086-1107), so only used rows are compared.
+ * One launch for the batch (k_find_rows: a lane per row, the used rows' dense run of the column's
+ * vector read, one ballot per query) on the world's stream, the masks back in one pinned copy; the
+ * staging buffers are the world's and grow on demand.  The answer is the reference's NOW, by the
+ * read-your-writes rule of nfk_get_records: a find whose (object, record) has queued SetRecord* /
+ * AddRow / Remove / ClearRecord calls in this window is answered on the host — the device's mask
+ * and column, the queued calls replayed in call order, then the comparison.  An object that
+ * entered in this window is read from the import buffer.  Queues nothing, changes nothing.
+ * nfk_find_rows_obj takes object indices (nfk_query_objects' hits, ev_obj) instead of NFGUIDs.
+ * NFK_ERR_ARG: a null argument, n < 0, a bad record or column; NFK_ERR_STATE before nfk_commit;
+ * NFK_ERR_NOTFOUND: an unknown (or destroyed) object.  The caller tests the column's type against
+ * its argument's (the reference returns -1 there, RC:837 / RC:880); the bits are compared as the
+ * column's type says. */
+int nfk_find_rows(void* world, int32_t n, const int64_t* guid_head, const int64_t* guid_data, const int32_t* rec,
+                  const int32_t* col, const uint64_t* bits, uint64_t* masks);
+int nfk_find_rows_obj(void* world, int32_t n, const int32_t* obj, const int32_t* rec, const int32_t* col,
+                      const uint64_t* bits, uint64_t* masks);
+/* the last nfk_find_rows / nfk_find_rows_obj of the world: its launch's device time in ms (0 unless
+ * nfk_set_profiling is on), the bytes read back and the finds answered on the host (each pointer
+ * may be null) */
+int nfk_find_stats(void* world, double* kernel_ms, int64_t* bytes, int32_t* n_host);
+
 /* ---- schema specialisation ----
  * At nfk_commit k_tick is compiled for the world's schema (its heartbeat programs as straight-line
  * code, its working set and event tables as constants) with hipRTC for gfx950, from the same

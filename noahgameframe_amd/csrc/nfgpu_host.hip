@@ -317,6 +317,17 @@ struct World {
     std::unordered_set<uint64_t> known_groups;
     std::unordered_set<int32_t> known_scenes;
     hipEvent_t q_ev[2] = {nullptr, nullptr};
+    // record finds (nfk_find_rows): the batch's descriptors and row masks on the device and in
+    // pinned host memory (descriptors first, masks behind them), both grown on demand; the last
+    // call's figures for nfk_find_stats
+    void* f_dev = nullptr;
+    size_t f_dcap = 0;
+    char* f_pin = nullptr;
+    size_t f_pcap = 0;
+    hipEvent_t f_ev[2] = {nullptr, nullptr};
+    double f_kernel_ms = 0;
+    int64_t f_bytes = 0;
+    int32_t f_host = 0;
 
     bool profiling = false;
     std::vector<PendingTiming> pend;
@@ -1858,6 +1869,10 @@ int nfk_destroy(void* world) {
     if (w->chain_pin) (void)hipHostFree(w->chain_pin);
     if (w->q_dev) (void)hipFree(w->q_dev);
     if (w->q_pin) (void)hipHostFree(w->q_pin);
+    if (w->f_dev) (void)hipFree(w->f_dev);
+    if (w->f_pin) (void)hipHostFree(w->f_pin);
+    for (auto e : w->f_ev)
+        if (e) (void)hipEventDestroy(e);
     for (auto e : w->q_ev)
         if (e) (void)hipEventDestroy(e);
     for (auto& p : w->pend) {
@@ -2560,6 +2575,47 @@ int nfk_get_used_rows(void* world, int32_t n, const int64_t* gh, const int64_t* 
     return NFK_OK;
 }
 
+// This window's queued calls on (object o, record r) replayed in call order on its used-row mask u
+// and on column col's cells c[rows] in ROW order: SetRecord* through RC:182 / RC:243 on the row's
+// used state at that call, AddRow / Remove / ClearRecord on the mask (RC:111, RC:1086, RC:1109).  A
+// Remove leaves the cell's value behind (RC:1086-1107); an AddRow without values writes 0.  A row's
+// result depends on no other row's cell.  Shared by nfk_get_records and nfk_find_rows.
+static void replay_column(const World* w, int32_t o, int32_t r, int32_t col, uint64_t& u, uint64_t* c) {
+    auto it = w->rq_index.find(((uint64_t)o << 3) | (uint32_t)r);
+    if (it == w->rq_index.end()) return;
+    const int32_t rows = w->tab.rec_rows[r];
+    for (uint32_t k : it->second) {
+        const World::RSOp& x = w->rsq[k];
+        const int xr = (int)((x.rrc >> 8) & 0xFF), xc = (int)(x.rrc & 0xFF);
+        if (x.op == 0) {
+            if (xc != col || !((u >> xr) & 1)) continue;
+            const uint64_t b = x.bits;
+            if (w->rec_ctype[r][col]) {
+                double bd, cd;
+                memcpy(&bd, &b, 8);
+                memcpy(&cd, &c[xr], 8);
+                const double df = bd - cd;
+                if (!(df < 0.001 && df > -0.001)) c[xr] = b;
+            } else {
+                c[xr] = b;
+            }
+        } else if (x.op == 1) {
+            int rr = xr;
+            if (xr == 0xFF) {
+                const uint64_t fr = ~u & (rows >= 64 ? ~0ull : ((1ull << rows) - 1));
+                if (!fr) continue;
+                rr = __builtin_ctzll(fr);
+            }
+            u |= 1ull << rr;
+            c[rr] = x.aux == 0xFFFFFFFFu ? 0ull : w->rvals[(size_t)x.aux * NFK_MAX_REC_COLS + col];
+        } else if (x.op == 2) {
+            u &= ~(1ull << xr);
+        } else {
+            u = 0;
+        }
+    }
+}
+
 int nfk_get_records(void* world, int32_t n, const int64_t* gh, const int64_t* gd, const int32_t* rec,
                     const int32_t* row, const int32_t* col, uint64_t* bits) {
     World* w = (World*)world;
@@ -2624,46 +2680,190 @@ int nfk_get_records(void* world, int32_t n, const int64_t* gh, const int64_t* gd
         for (size_t q = 0; q < at.size(); q++) cv[at[q]] = got[q];
     }
     for (int32_t i = 0; i < n; i++) {
-        const int32_t o = obj[i], r = rec[i], rows = w->tab.rec_rows[r];
-        uint64_t u = um[i], c = cv[i];
-        // this window's queued calls on the record replayed in call order: SetRecord* through
-        // RC:182 / RC:243 on the row's used state at that call, AddRow / Remove / ClearRecord on the
-        // used-row mask (RC:111, RC:1086, RC:1109)
-        auto it = w->rq_index.find(((uint64_t)o << 3) | (uint32_t)r);
-        if (it != w->rq_index.end())
-            for (uint32_t k : it->second) {
-                const World::RSOp& x = w->rsq[k];
-                const int xr = (int)((x.rrc >> 8) & 0xFF), xc = (int)(x.rrc & 0xFF);
-                if (x.op == 0) {
-                    if (xr != row[i] || xc != col[i] || !((u >> xr) & 1)) continue;
-                    const uint64_t b = x.bits;
-                    if (w->rec_ctype[r][col[i]]) {
-                        double bd, cd;
-                        memcpy(&bd, &b, 8);
-                        memcpy(&cd, &c, 8);
-                        const double df = bd - cd;
-                        if (!(df < 0.001 && df > -0.001)) c = b;
-                    } else {
-                        c = b;
-                    }
-                } else if (x.op == 1) {
-                    int rr = xr;
-                    if (xr == 0xFF) {
-                        const uint64_t fr = ~u & (rows >= 64 ? ~0ull : ((1ull << rows) - 1));
-                        if (!fr) continue;
-                        rr = __builtin_ctzll(fr);
-                    }
-                    u |= 1ull << rr;
-                    if (rr == row[i]) c = x.aux == 0xFFFFFFFFu ? 0ull : w->rvals[(size_t)x.aux * NFK_MAX_REC_COLS + col[i]];
-                } else if (x.op == 2) {
-                    u &= ~(1ull << xr);
-                } else {
-                    u = 0;
-                }
-            }
+        uint64_t u = um[i], c[64] = {};
+        c[row[i]] = cv[i];
+        replay_column(w, obj[i], rec[i], col[i], u, c);
         // NFCRecord::GetInt / GetFloat of an unused row (RC:623): 0
-        bits[i] = ((u >> row[i]) & 1) ? c : 0;
+        bits[i] = ((u >> row[i]) & 1) ? c[row[i]] : 0;
     }
+    return NFK_OK;
+}
+
+// ---- record finds (nfk_find_rows): NFCRecord::FindInt / FindFloat (RC:830-899) ----
+// device addresses of object o's record r: its cells [cols][rows] and its used-row mask (its row of
+// the import buffer when it entered in this window, else its slot; used_addr)
+static int rec_addrs(World* w, int32_t o, int32_t r, const uint64_t** cells, const uint64_t** used) {
+    const size_t rows = (size_t)w->tab.rec_rows[r], cols = (size_t)w->tab.rec_cols[r];
+    if (w->src_row[o] >= 0) {
+        int64_t off = w->n_pw + 4 * w->cfg.n_kind;
+        for (int x = 0; x < r; x++) off += (int64_t)w->tab.rec_rows[x] * w->tab.rec_cols[x] + 1;
+        *cells = w->ins_rows + (size_t)w->src_row[o] * w->row_words + off;
+        *used = *cells + rows * cols;
+    } else if (w->slot_of_obj[o] >= 0) {
+        *cells = w->d.rcells[r] + (size_t)w->slot_of_obj[o] * cols * rows;
+        *used = w->d.rused[r] + w->slot_of_obj[o];
+    } else {
+        return fail(NFK_ERR_STATE, "object without a slot");
+    }
+    return NFK_OK;
+}
+
+// the finds of resolved objects (obj[i] < 0: unknown; gh / gd for the message, or null)
+static int find_rows(World* w, int32_t n, const int32_t* obj, const int64_t* gh, const int64_t* gd, const int32_t* rec,
+                     const int32_t* col, const uint64_t* bits, uint64_t* masks) {
+    w->f_kernel_ms = 0;
+    w->f_bytes = 0;
+    w->f_host = 0;
+    int max_rows = 1;
+    for (int32_t i = 0; i < n; i++) {
+        if (obj[i] < 0)
+            return fail(NFK_ERR_NOTFOUND, gh ? "There is no object " + std::to_string(gh[i]) + "-" + std::to_string(gd[i])
+                                             : "no object index");
+        const int32_t r = rec[i];
+        if (r < 0 || r >= w->cfg.n_rec || !w->rec_defined[r]) return fail(NFK_ERR_ARG, "bad record");
+        if (col[i] < 0 || col[i] >= w->tab.rec_cols[r]) return fail(NFK_ERR_ARG, "record column out of range");
+        max_rows = std::max(max_rows, (int)w->tab.rec_rows[r]);
+    }
+    if (n == 0) return NFK_OK;
+    int lg = 0;
+    while ((1 << lg) < max_rows) lg++;  // (rows <= 64: lg <= 6)
+
+    // descriptors in pinned memory, the masks behind them; a query whose record has queued calls
+    // in this window is left out of the batch (host: below)
+    const size_t o_m = align16((size_t)n * sizeof(FindDev)), tot = o_m + (size_t)n * 8;
+    if (int r = dev_reserve(w, &w->f_dev, &w->f_dcap, tot)) return r;
+    if (tot > w->f_pcap) {
+        if (w->f_pin) HIPCHK(hipHostFree(w->f_pin));
+        w->f_pin = nullptr;
+        const size_t c = std::max(tot, w->f_pcap + w->f_pcap / 2);
+        w->f_pcap = 0;  // (until the new buffer exists)
+        HIPCHK(hipHostMalloc((void**)&w->f_pin, c, hipHostMallocDefault));
+        w->f_pcap = c;
+    }
+    FindDev* hq = (FindDev*)w->f_pin;
+    const uint64_t* hm = (const uint64_t*)(w->f_pin + o_m);
+    std::vector<int32_t> host;  // queries answered on the host
+    const bool queued = !w->rq_index.empty();
+    int32_t nd = 0;
+    for (int32_t i = 0; i < n; i++) {
+        const int32_t o = obj[i], r = rec[i];
+        if (queued && w->rq_index.count(((uint64_t)o << 3) | (uint32_t)r)) {
+            host.push_back(i);
+            continue;
+        }
+        const uint64_t *cells, *used;
+        if (int e = rec_addrs(w, o, r, &cells, &used)) return e;
+        FindDev f;
+        f.used = (uint64_t)(uintptr_t)used;
+        f.colv = (uint64_t)(uintptr_t)(cells + (size_t)col[i] * w->tab.rec_rows[r]);
+        f.rows = w->tab.rec_rows[r];
+        f.flt = w->rec_ctype[r][col[i]] ? 1 : 0;
+        f.arg = bits[i];
+        hq[nd++] = f;
+    }
+    if (nd) {
+        char* D = (char*)w->f_dev;
+        const bool timed = w->profiling;
+        if (timed)
+            for (auto& e : w->f_ev)
+                if (!e) HIPCHK(hipEventCreate(&e));
+        HIPCHK(hipMemcpyAsync(D, hq, (size_t)nd * sizeof(FindDev), hipMemcpyHostToDevice, w->stream));
+        if (timed) HIPCHK(hipEventRecord(w->f_ev[0], w->stream));
+        const int64_t threads = (int64_t)nd << lg;
+        hipLaunchKernelGGL(k_find_rows, dim3((unsigned)((threads + kTPB - 1) / kTPB)), dim3(kTPB), 0, w->stream,
+                           (const FindDev*)D, nd, lg, (uint64_t*)(D + o_m));
+        HIPCHK(hipGetLastError());
+        if (timed) HIPCHK(hipEventRecord(w->f_ev[1], w->stream));
+        HIPCHK(hipMemcpyAsync(w->f_pin + o_m, D + o_m, (size_t)nd * 8, hipMemcpyDeviceToHost, w->stream));
+        HIPCHK(hipStreamSynchronize(w->stream));
+        w->f_bytes = (int64_t)nd * 8;
+        if (timed) {
+            float ms = 0;
+            HIPCHK(hipEventElapsedTime(&ms, w->f_ev[0], w->f_ev[1]));
+            w->f_kernel_ms = ms;
+        }
+        if (host.empty()) {
+            memcpy(masks, hm, (size_t)n * 8);
+        } else {
+            size_t h = 0;
+            int32_t k = 0;
+            for (int32_t i = 0; i < n; i++) {
+                if (h < host.size() && host[h] == i) h++;
+                else masks[i] = hm[k++];
+            }
+        }
+    }
+    if (host.empty()) return NFK_OK;
+
+    // read-your-writes: the device's mask and the column's used cells (two gathers for all of
+    // them), the cells put in row order, the queued calls replayed, then the comparison
+    w->f_host = (int32_t)host.size();
+    std::vector<uint64_t> addr(host.size()), um(host.size());
+    std::vector<const uint64_t*> colv(host.size());
+    for (size_t j = 0; j < host.size(); j++) {
+        const int32_t i = host[j];
+        const uint64_t *cells, *used;
+        if (int e = rec_addrs(w, obj[i], rec[i], &cells, &used)) return e;
+        addr[j] = (uint64_t)(uintptr_t)used;
+        colv[j] = cells + (size_t)col[i] * w->tab.rec_rows[rec[i]];
+    }
+    if (int e = read_abs(w, addr, um.data())) return e;
+    addr.clear();
+    for (size_t j = 0; j < host.size(); j++) {
+        um[j] &= rec_rowm(w->tab.rec_rows[rec[host[j]]]);
+        for (int p = 0, np = __builtin_popcountll(um[j]); p < np; p++) addr.push_back((uint64_t)(uintptr_t)(colv[j] + p));
+    }
+    std::vector<uint64_t> cv(addr.size());
+    if (int e = read_abs(w, addr, cv.data())) return e;
+    size_t at = 0;
+    for (size_t j = 0; j < host.size(); j++) {
+        const int32_t i = host[j], r = rec[i], rows = w->tab.rec_rows[r];
+        uint64_t u = um[j], c[64] = {};
+        for (int row = 0; row < rows; row++)
+            if ((u >> row) & 1) c[row] = cv[at++];  // (the used rows first, in row order: rec_pos)
+        replay_column(w, obj[i], r, col[i], u, c);
+        uint64_t m = 0;
+        double a;
+        memcpy(&a, &bits[i], 8);
+        for (int row = 0; row < rows; row++) {
+            if (!((u >> row) & 1)) continue;
+            bool hit = c[row] == bits[i];
+            if (w->rec_ctype[r][col[i]]) {
+                double v;
+                memcpy(&v, &c[row], 8);
+                hit = v == a;
+            }
+            m |= (uint64_t)hit << row;
+        }
+        masks[i] = m;
+    }
+    return NFK_OK;
+}
+
+int nfk_find_rows(void* world, int32_t n, const int64_t* gh, const int64_t* gd, const int32_t* rec, const int32_t* col,
+                  const uint64_t* bits, uint64_t* masks) {
+    World* w = (World*)world;
+    if (!w || n < 0 || (n && (!gh || !gd || !rec || !col || !bits || !masks))) return fail(NFK_ERR_ARG, "null argument");
+    if (!w->committed) return fail(NFK_ERR_STATE, "commit first");
+    std::vector<int32_t> obj(n);
+    if (int rl = find_many_par(w, n, gh, gd, obj.data())) return rl;
+    return find_rows(w, n, obj.data(), gh, gd, rec, col, bits, masks);
+}
+
+int nfk_find_rows_obj(void* world, int32_t n, const int32_t* obj, const int32_t* rec, const int32_t* col,
+                      const uint64_t* bits, uint64_t* masks) {
+    World* w = (World*)world;
+    if (!w || n < 0 || (n && (!obj || !rec || !col || !bits || !masks))) return fail(NFK_ERR_ARG, "null argument");
+    if (!w->committed) return fail(NFK_ERR_STATE, "commit first");
+    return find_rows(w, n, live_objects(w, n, obj), nullptr, nullptr, rec, col, bits, masks);
+}
+
+int nfk_find_stats(void* world, double* kernel_ms, int64_t* bytes, int32_t* n_host) {
+    World* w = (World*)world;
+    if (!w) return fail(NFK_ERR_ARG, "null world");
+    if (kernel_ms) *kernel_ms = w->f_kernel_ms;
+    if (bytes) *bytes = w->f_bytes;
+    if (n_host) *n_host = w->f_host;
     return NFK_OK;
 }
 

@@ -2371,4 +2371,40 @@ __global__ __launch_bounds__(1024) void k_query_scan(const uint32_t* __restrict_
     for (int q = threadIdx.x; q <= n_q; q += 1024) off[q] = out[tile0[q]];
 }
 
+// ---------------------------------------------------------------------------------
+// Record finds (nfk_find_rows): NFCRecord::FindInt / FindFloat (RC:830-899) of a batch of (object,
+// record, column, argument) queries.  A lane is a row: a query takes a group of G = 1 << lg lanes
+// (G: the power of two >= the batch's largest rows, so 64 / G queries per wave), every lane of the
+// group reads the query's used-row mask, a lane whose row is used reads its cell — place
+// popcount(used & below) of the column's vector, the dense run at its start (rec_pos) — and
+// compares; the group's G bits of the wave's ballot are the query's answer, stored by its first
+// lane.  No atomics, no LDS, no workgroup waits on another.
+struct FindDev {
+    uint64_t used;  // absolute address of the used-row mask
+    uint64_t colv;  // absolute address of the column's [rows] vector
+    int32_t rows;
+    int32_t flt;    // f64 column: the C == on doubles (NaN equals nothing, -0.0 equals 0.0)
+    uint64_t arg;
+};  // 32 bytes
+static_assert(sizeof(FindDev) == 32, "FindDev is 32 bytes");
+__global__ __launch_bounds__(kTPB) void k_find_rows(const FindDev* __restrict__ qs, int32_t n, int lg,
+                                                    uint64_t* __restrict__ masks) {
+    const int64_t t = (int64_t)blockIdx.x * kTPB + threadIdx.x;
+    const int64_t q = t >> lg;
+    const int lane = (int)(threadIdx.x & 63), G = 1 << lg, row = lane & (G - 1);
+    bool hit = false;
+    if (q < n) {  // (no early return: every lane of the wave takes part in the ballot)
+        const FindDev f = qs[q];
+        if (row < f.rows) {
+            const uint64_t used = *(const uint64_t*)(uintptr_t)f.used & rec_rowm(f.rows);
+            if ((used >> row) & 1) {
+                const uint64_t c = ((const uint64_t*)(uintptr_t)f.colv)[__builtin_popcountll(used & ((1ull << row) - 1))];
+                hit = f.flt ? __longlong_as_double((long long)c) == __longlong_as_double((long long)f.arg) : c == f.arg;
+            }
+        }
+    }
+    const unsigned long long b = __ballot(hit);
+    if (q < n && row == 0) masks[q] = (b >> (lane - row)) & rec_rowm(G);
+}
+
 }  // namespace nfgpu

@@ -894,6 +894,107 @@ double NFGPUKernelModule::GetRecordFloat(const NFGUID& self, const std::string& 
     return v;
 }
 
+// ---- record finds (RC:554-613, RC:778-910) ----
+// nfk_find_rows is looked up at first use, like the scene queries' entry points (nfgpu_symbol)
+void NFGPUKernelModule::FindRows(const std::vector<RowFind>& finds, std::vector<RowHits>& hits) {
+    using Fn = int (*)(void*, int32_t, const int64_t*, const int64_t*, const int32_t*, const int32_t*, const uint64_t*,
+                       uint64_t*);
+    static const Fn fn = (Fn)nfgpu_symbol("nfk_find_rows");
+    if (!fn) throw std::runtime_error("nfk_find_rows: the nfgpu library has no such entry point");
+    Flush();  // (the buffered Set calls first: call order)
+    hits.assign(finds.size(), RowHits{});
+    std::vector<int64_t> gh, gd;
+    std::vector<int32_t> rec, col;
+    std::vector<uint64_t> bits;
+    std::vector<size_t> at;
+    for (size_t i = 0; i < finds.size(); i++) {
+        const RowFind& f = finds[i];
+        auto it = record_id_.find(f.strRecordName);
+        const TDATA_TYPE t = f.value.GetType();
+        // ValidCol and the column's type (RC:832-840, RC:875-883); "There is no object" (KM:487)
+        if (!committed_ || it == record_id_.end() || ObjectIndex(f.self) < 0 || f.nCol < 0 ||
+            f.nCol >= (int)records_[it->second].cols.size() || (t != TDATA_INT && t != TDATA_FLOAT) ||
+            records_[it->second].cols[f.nCol] != t) {
+            hits[i].invalid = true;
+            continue;
+        }
+        gh.push_back(f.self.nHead64);
+        gd.push_back(f.self.nData64);
+        rec.push_back(it->second);
+        col.push_back(f.nCol);
+        bits.push_back(t == TDATA_INT ? (uint64_t)f.value.GetInt() : bits_of(f.value.GetFloat()));
+        at.push_back(i);
+    }
+    if (at.empty()) return;
+    std::vector<uint64_t> m(at.size());
+    check(fn(world_, (int32_t)at.size(), gh.data(), gd.data(), rec.data(), col.data(), bits.data(), m.data()),
+          "nfk_find_rows");
+    for (size_t j = 0; j < at.size(); j++) hits[at[j]].mask = m[j];
+}
+
+static int append_rows(const NFGPUKernelModule::RowHits& h, std::vector<int>& varResult) {
+    if (h.invalid) return -1;
+    for (uint64_t m = h.mask; m; m &= m - 1) varResult.push_back(__builtin_ctzll(m));
+    return (int)varResult.size();  // varResult.GetCount() (RC:856): what the list held before counts
+}
+
+int NFGPUKernelModule::FindInt(const NFGUID& self, const std::string& strRecordName, int nCol, int64_t value,
+                               std::vector<int>& varResult) {
+    TData v;
+    v.type = TDATA_INT;
+    v.i = value;
+    std::vector<RowHits> h;
+    FindRows({RowFind{self, strRecordName, nCol, v}}, h);
+    return append_rows(h[0], varResult);
+}
+
+int NFGPUKernelModule::FindFloat(const NFGUID& self, const std::string& strRecordName, int nCol, double value,
+                                 std::vector<int>& varResult) {
+    TData v;
+    v.type = TDATA_FLOAT;
+    v.f = value;
+    std::vector<RowHits> h;
+    FindRows({RowFind{self, strRecordName, nCol, v}}, h);
+    return append_rows(h[0], varResult);
+}
+
+int NFGPUKernelModule::FindRowByColValue(const NFGUID& self, const std::string& strRecordName, int nCol,
+                                         const std::vector<TData>& var, std::vector<int>& varResult) {
+    // var.Type(0) against the column (RC:785; an empty list: TDATA_UNKNOWN), then the value at index
+    // nCol of var (RC:794): NFCDataList::Int / Float give 0 past the end or for another type
+    const TDATA_TYPE t = var.empty() ? TDATA_UNKNOWN : var[0].GetType();
+    const TData* e = nCol >= 0 && (size_t)nCol < var.size() ? &var[(size_t)nCol] : nullptr;
+    if (t == TDATA_INT) return FindInt(self, strRecordName, nCol, e ? e->GetInt() : 0, varResult);
+    if (t == TDATA_FLOAT) return FindFloat(self, strRecordName, nCol, e ? e->GetFloat() : 0.0, varResult);
+    return -1;  // (string / object columns: device records hold none)
+}
+
+bool NFGPUKernelModule::QueryRow(const NFGUID& self, const std::string& strRecordName, int nRow,
+                                 std::vector<TData>& varList) {
+    Flush();  // (the buffered Set calls first: call order)
+    auto it = record_id_.find(strRecordName);
+    if (!committed_ || it == record_id_.end() || ObjectIndex(self) < 0) return false;
+    const RecordDef& rd = records_[it->second];
+    if (nRow < 0 || nRow >= rd.rows) return false;                    // ValidRow (RC:556)
+    if (!((UsedRows(self, it->second) >> nRow) & 1)) return false;  // IsUsed (RC:561)
+    const size_t nc = rd.cols.size();
+    std::vector<int64_t> gh(nc, self.nHead64), gd(nc, self.nData64);
+    std::vector<int32_t> rec(nc, it->second), row(nc, nRow), col(nc);
+    std::iota(col.begin(), col.end(), 0);
+    std::vector<uint64_t> b(nc);
+    check(nfk_get_records(world_, (int32_t)nc, gh.data(), gd.data(), rec.data(), row.data(), col.data(), b.data()),
+          "nfk_get_records");
+    varList.clear();
+    for (size_t c = 0; c < nc; c++) {
+        TData v;
+        v.type = rd.cols[c];
+        if (v.type == TDATA_INT) v.i = (int64_t)b[c];
+        else memcpy(&v.f, &b[c], 8);
+        varList.push_back(v);
+    }
+    return true;
+}
+
 bool NFGPUKernelModule::SetPropertyFloat(const NFGUID& self, const std::string& name, double v) {
     const int p = prop_ix_.find(name);
     if (!committed_ || p < 0 || props_[(size_t)p].type != TDATA_FLOAT) return false;

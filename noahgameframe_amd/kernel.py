@@ -130,6 +130,8 @@ def load_library(path=LIB_PATH):
         "nfk_get_objects": [VP, I32, VP, VP, VP, VP, VP], "nfk_read_object": [VP, I32, VP, VP],
         "nfk_read_events_obj": [VP, VP, VP], "nfk_record_rows": [VP, I32, VP, VP, VP, VP, VP, VP],
         "nfk_query_objects": [VP, I32, VP, P(QueryResult)], "nfk_online_count": [VP, I32, I32, VP],
+        "nfk_find_rows": [VP, I32, VP, VP, VP, VP, VP, VP], "nfk_find_rows_obj": [VP, I32, VP, VP, VP, VP, VP],
+        "nfk_find_stats": [VP, VP, VP, VP], "nfk_get_used_rows": [VP, I32, VP, VP, VP, VP],
     }
     for name, args in sig.items():
         if not hasattr(lib, name) and os.environ.get("NFGPU_LIB"):
@@ -187,6 +189,7 @@ class NFKernelModule:
         fl = np.ascontiguousarray(flags_per_class, np.uint8)
         self._chk(self.lib.nfk_define_record(self.h, rec, rows, cols, _p(ct), _p(fl)))
         self.rec_shape[rec] = (cols, rows)
+        self.rec_types = {**getattr(self, "rec_types", {}), rec: [int(t) for t in ct[:cols]]}
 
     def define_kind(self, kind, ops):
         ops = np.ascontiguousarray(ops)
@@ -296,6 +299,75 @@ class NFKernelModule:
         out = np.zeros(len(a[0]), np.uint64)
         self._chk(self.lib.nfk_get_records(self.h, len(a[0]), *[_p(x) for x in a], _p(out)))
         return out
+
+    # ---- NFCRecord::FindInt / FindFloat / QueryRow (RC:830-899, RC:554) ----
+    def find_rows(self, guid_head, guid_data, rec, col, bits, stats=None):
+        """nfk_find_rows: n (object, record, column, argument bits) finds -> uint64 row masks (bit r:
+        row r is used and its cell equals the argument under the column's type), read-your-writes.
+        stats: a dict that receives the launch's device time (kernel_ms, with set_profiling(True)),
+        the bytes read back and the finds answered on the host (n_host)."""
+        a = [np.ascontiguousarray(x, t) for x, t in
+             ((guid_head, np.int64), (guid_data, np.int64), (rec, np.int32), (col, np.int32), (bits, np.uint64))]
+        out = np.zeros(len(a[0]), np.uint64)
+        self._chk(self.lib.nfk_find_rows(self.h, len(a[0]), *[_p(x) for x in a], _p(out)))
+        self._find_stats(stats)
+        return out
+
+    def find_rows_obj(self, obj, rec, col, bits, stats=None):
+        """nfk_find_rows_obj: find_rows by object index (query_objects' hits, the outputs' ev_obj)"""
+        a = [np.ascontiguousarray(x, t) for x, t in
+             ((obj, np.int32), (rec, np.int32), (col, np.int32), (bits, np.uint64))]
+        out = np.zeros(len(a[0]), np.uint64)
+        self._chk(self.lib.nfk_find_rows_obj(self.h, len(a[0]), *[_p(x) for x in a], _p(out)))
+        self._find_stats(stats)
+        return out
+
+    def _find_stats(self, stats):
+        if stats is None:
+            return
+        ms, by, nh = ctypes.c_double(), ctypes.c_int64(), ctypes.c_int32()
+        self._chk(self.lib.nfk_find_stats(self.h, ctypes.byref(ms), ctypes.byref(by), ctypes.byref(nh)))
+        stats["kernel_ms"], stats["bytes"], stats["n_host"] = ms.value, by.value, nh.value
+
+    def _find(self, guid, rec, col, bits, want_float, result):
+        """the reference's return: -1 (nothing appended) for an unknown object or record, an invalid
+        column or a column of another type; else the hits appended and result's total size (RC:856)"""
+        shape = self.rec_shape.get(rec)
+        types = getattr(self, "rec_types", {}).get(rec)
+        if shape is None or col < 0 or col >= shape[0]:
+            return -1
+        if types is not None and bool(types[col]) != want_float:
+            return -1
+        try:
+            m = int(self.find_rows([guid[0]], [guid[1]], [rec], [col], [bits])[0])
+        except NFKError as e:
+            if e.code != -7:   # (NFK_ERR_NOTFOUND: "There is no object", the reference's -1)
+                raise
+            return -1
+        result.extend(r for r in range(64) if (m >> r) & 1)
+        return len(result)
+
+    def FindInt(self, guid, rec, col, value, result):
+        """NFCRecord::FindInt (RC:830): rows whose int cell equals value, appended to result"""
+        return self._find(guid, rec, col, np.int64(value).view(np.uint64), False, result)
+
+    def FindFloat(self, guid, rec, col, value, result):
+        """NFCRecord::FindFloat (RC:873): rows whose f64 cell == value, appended to result"""
+        return self._find(guid, rec, col, np.float64(value).view(np.uint64), True, result)
+
+    def QueryRow(self, guid, rec, row):
+        """NFCRecord::QueryRow (RC:554): the row's cells as raw 64-bit patterns [cols], or None for
+        an invalid or unused row (the reference's false)"""
+        shape = self.rec_shape.get(rec)
+        if shape is None or row < 0 or row >= shape[1]:
+            return None
+        used = np.zeros(1, np.uint64)
+        gh, gd = np.array([guid[0]], np.int64), np.array([guid[1]], np.int64)
+        self._chk(self.lib.nfk_get_used_rows(self.h, 1, _p(gh), _p(gd), _p(np.array([rec], np.int32)), _p(used)))
+        if not (int(used[0]) >> row) & 1:
+            return None
+        cols = shape[0]
+        return self.get_records([guid[0]] * cols, [guid[1]] * cols, [rec] * cols, [row] * cols, list(range(cols)))
 
     def SetRecordInt(self, guid, rec, row, col, value):
         self.set_records([guid[0]], [guid[1]], [rec], [row], [col], [np.int64(value).view(np.uint64)], [0])
