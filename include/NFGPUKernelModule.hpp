@@ -40,6 +40,9 @@
 //     are resolved; on the C-ABI nfk_define_record of it comes before nfk_define_kind.
 //   * String / Vector properties stay host-side (not on the frame path); object (NFGUID) properties
 //     are device columns like the int / float ones.
+//   * An enter view (GetEnterViews / GetGroupEnterViews: the OnPropertyEnter / OnRecordEnter payload)
+//     holds the device properties and records only: host-side string and vector properties are NOT
+//     in it, the host packs them itself.
 #pragma once
 #include <algorithm>
 #include <atomic>
@@ -434,6 +437,27 @@ public:
     struct RowFind { NFGUID self; std::string strRecordName; int nCol = 0; TData value; };
     struct RowHits { uint64_t mask = 0; bool invalid = false; };
     void FindRows(const std::vector<RowFind>& finds, std::vector<RowHits>& hits);
+    // ---- enter views: what NFCGameServerNet_ServerModule::OnPropertyEnter / OnRecordEnter pack for an
+    // object that comes into a recipient's view (NFCSceneAOIModule::OnGroupEvent / OnSceneEvent /
+    // OnClassCommonEvent hand them out).  bPrivate: the recipient is the object itself (the entries
+    // flagged private), else the entries flagged public.  Properties in name order (std::string's <,
+    // the reference's std::map walk), only those whose value is not null (NFCProperty::Changed(): an
+    // int != 0, a float beyond +-0.001, a non-null NFGUID); every record in view in name order, also
+    // one without a used row, with its used rows ascending x columns.  One nfk_snapshot_objects_obj
+    // call per batch after a Flush(), so the answer is the reference's now.  Host-side string and
+    // vector properties are NOT in a view: they stay with the host, which packs them itself.
+    struct EnterProperty { const std::string* name; TData value; };
+    struct EnterRecord { const std::string* name; uint64_t used; std::vector<TData> cells; /* used rows ascending x columns, row-major as the reference packs */ };
+    struct EnterView { NFGUID self; bool bPrivate; std::vector<EnterProperty> properties; std::vector<EnterRecord> records; };
+    // an object this module does not have yields an empty view with self null
+    void GetEnterViews(const std::vector<NFGUID>& objects, const std::vector<uint8_t>& bPrivate, std::vector<EnterView>& out);
+    // what AOI:396-455 hands out for `self` arriving in (scene, group): one nfk_query_objects batch
+    // (the group's players, then its other objects, both without self) and one snapshot batch; out
+    // holds the public view of every object of objectsNoSelf in list order (what self receives when
+    // it is a player) and last the public view of self (what every player of playersNoSelf
+    // receives).  false, nothing returned, for a group that does not exist (as GetGroupObjectList).
+    bool GetGroupEnterViews(const NFGUID& self, int nSceneID, int nGroupID, std::vector<NFGUID>& playersNoSelf,
+                            std::vector<NFGUID>& objectsNoSelf, std::vector<EnterView>& out);
     // NFCKernelModule::SwitchScene (KM:901-951); writes SceneID/GroupID/X/Y/Z when the schema has
     // them; like the reference, fOrient and arg are not used
     bool SwitchScene(const NFGUID& self, int nTargetSceneID, int nTargetGroupID, float fX, float fY, float fZ,

@@ -209,7 +209,8 @@ int nfk_destroy(void* world);
 const char* nfk_last_error(void);
 
 /* ---- schema: NFIClassModule property/record definitions (KM:137-189) ---- */
-int nfk_set_prop_flags(void* world, int32_t cls, const uint8_t* flags /* [n_int+n_flt] */);
+int nfk_set_prop_flags(void* world, int32_t cls, const uint8_t* flags /* [n_int+n_flt+n_obj]: the object
+                                                                         properties' flags behind the others */);
 int nfk_define_record(void* world, int32_t rec, int32_t rows, int32_t cols,
                       const uint8_t* col_types /* [cols] 0=int64 1=f64 */,
                       const uint8_t* flags_per_class /* [n_class] */);
@@ -542,6 +543,64 @@ int nfk_find_rows_obj(void* world, int32_t n, const int32_t* obj, const int32_t*
  * nfk_set_profiling is on), the bytes read back and the finds answered on the host (each pointer
  * may be null) */
 int nfk_find_stats(void* world, double* kernel_ms, int64_t* bytes, int32_t* n_host);
+
+/* ---- enter snapshots: the payloads of NFCGameServerNet_ServerModule::OnPropertyEnter (:271-393) and
+ * OnRecordEnter (:395-554), which NFCSceneAOIModule::OnGroupEvent / OnSceneEvent / OnClassCommonEvent
+ * hand to the recipients of an object that comes into view ----
+ * n (object, view) requests answered in one call.  NFK_VIEW_PRIVATE (the recipient is the object
+ * itself) takes the entries whose flags have NFK_PRIVATE, NFK_VIEW_PUBLIC those with NFK_PUBLIC; an
+ * entry with both is in both views, NFK_UPLOAD plays no part.  The flags are Tables::pflags[class][pid]
+ * (nfk_set_prop_flags: all three property types) and the records' flags_per_class.
+ * Properties: the walk's order (nfk_set_snapshot_order: the reference walks a std::map by name; the
+ * default is id order); a property is an entry only when NFCProperty::Changed() holds, that is
+ * !IsNullValue() (NFIDataList.h:160-221): an int != 0; an f64 v with v > 0.001 || v < -0.001 (0.001,
+ * -0.001, -0.0, denormals and NaN are not entries); an object with either half non-zero.
+ * Records: every record in view, in the walk's order, is one entry, also when it uses no row; its
+ * cells are those of its used rows, no null test (a cell of an unused row is never in it).
+ * Requests may repeat an object and come in any order; results are in request order.  The runs
+ * answered by the kernels (k_snap, k_snap_scan, k_snap_cells on the world's stream, one pinned
+ * copy back) are dense in request order; a request whose object has a queued SetProperty* /
+ * SetPropertyObject call (SwitchScene's among them) or a queued record call in this window, or that
+ * entered in this window (spawn / import), is answered on the host through the code of nfk_get_props /
+ * nfk_get_objects / nfk_get_records, with the same predicates, and its runs are appended behind the
+ * kernels' — hence (first, count) pairs, not a CSR.  The answer is the reference's NOW; the call
+ * waits for the world's stream, queues nothing and changes nothing a frame reads.
+ * NFK_ERR_ARG: a null argument (a null world's message says so), n < 0, a view that is neither
+ * constant; NFK_ERR_NOTFOUND: an unknown or destroyed object; NFK_ERR_STATE before nfk_commit;
+ * NFK_ERR_CAPACITY: the BOUND of the batch's property entries, record entries or cells does not fit
+ * 32 bits — every property in view taken as an entry, every row of every record in view as used
+ * (rows x cols cells), summed over the requests on the host before anything is allocated or
+ * launched, so the device's 32-bit counts cannot wrap; a batch whose real totals would fit is
+ * refused with its bound — or n > INT32_MAX / 3 (tested before an array is read).  NFK_ERR_DEVICE:
+ * the kernels counted more than that bound, an invariant check no batch can reach.  n == 0 launches
+ * nothing.  After any of these the world answers the next call. */
+#define NFK_VIEW_PUBLIC 1u
+#define NFK_VIEW_PRIVATE 2u
+typedef struct nfk_snapshot { /* world-owned pinned memory, valid until the next nfk_snapshot_* /
+                                 nfk_execute / nfk_execute_calls */
+    const uint32_t *p_first, *p_count; /* [n] request i's property entries: p_pid/p_bits/p_head[p_first[i] .. +p_count[i]) */
+    const int32_t* p_pid;              /* walk order */
+    const uint64_t* p_bits;            /* the word; an object property's data half */
+    const uint64_t* p_head;            /* an object property's head half, 0 otherwise; NULL when n_obj == 0 */
+    const uint32_t *r_first, *r_count; /* [n] request i's record entries */
+    const int32_t* r_rec;
+    const uint64_t* r_used;            /* used-row mask (may be 0) */
+    const uint32_t* r_cell;            /* first cell of the entry in cells[] */
+    const uint64_t* cells;             /* entry e: cells[r_cell[e] + c * popcount(r_used[e]) + k] = column c of
+                                          the k-th used row (column-major, as the device holds it) */
+    double kernel_ms;                  /* the launches' device time (0 unless nfk_set_profiling is on) */
+    int64_t bytes;                     /* read back */
+    int32_t n_host;                    /* requests answered on the host */
+} nfk_snapshot;
+int nfk_snapshot_objects(void* world, int32_t n, const int64_t* guid_head, const int64_t* guid_data,
+                         const uint8_t* view, nfk_snapshot* out);
+/* by object index (nfk_query_objects' hits, ev_obj) instead of NFGUID */
+int nfk_snapshot_objects_obj(void* world, int32_t n, const int32_t* obj, const uint8_t* view, nfk_snapshot* out);
+/* the walk's order: prop_order a permutation of the property ids [0, n_int + n_flt + n_obj),
+ * rec_order one of the record ids [0, n_rec); NULL: id order.  The world holds no names, so the
+ * caller gives the byte-wise name order of the reference's NFMapEx walk.  Before or after
+ * nfk_commit; NFK_ERR_ARG for anything that is not a permutation (nothing is changed then). */
+int nfk_set_snapshot_order(void* world, const int32_t* prop_order, const int32_t* rec_order);
 
 /* ---- schema specialisation ----
  * At nfk_commit k_tick is compiled for the world's schema (its heartbeat programs as straight-line

@@ -328,6 +328,22 @@ struct World {
     double f_kernel_ms = 0;
     int64_t f_bytes = 0;
     int32_t f_host = 0;
+    // enter snapshots (nfk_snapshot_objects): the walk's order (empty: id order), its table on the
+    // device (rebuilt when flags or order change), the batch's scratch (requests, counts, bases) and
+    // result region on the device, and the pinned buffer the nfk_snapshot pointers index
+    std::vector<int32_t> s_porder, s_rorder;
+    SnapTab s_tab{};
+    uint32_t s_cells_ub[NFK_MAX_CLASSES][2] = {};  // most cells of a request of (class, view)
+    SnapTab* s_tab_d = nullptr;
+    bool s_tab_dirty = true;
+    void* s_dev = nullptr;
+    size_t s_dcap = 0;
+    void* s_out = nullptr;
+    size_t s_ocap = 0;
+    char* s_pin = nullptr;
+    size_t s_pcap = 0;
+    hipEvent_t s_ev[4] = {nullptr, nullptr, nullptr, nullptr};
+    std::vector<uint8_t> s_mark;
 
     bool profiling = false;
     std::vector<PendingTiming> pend;
@@ -1873,6 +1889,12 @@ int nfk_destroy(void* world) {
     if (w->f_pin) (void)hipHostFree(w->f_pin);
     for (auto e : w->f_ev)
         if (e) (void)hipEventDestroy(e);
+    if (w->s_tab_d) (void)hipFree(w->s_tab_d);
+    if (w->s_dev) (void)hipFree(w->s_dev);
+    if (w->s_out) (void)hipFree(w->s_out);
+    if (w->s_pin) (void)hipHostFree(w->s_pin);
+    for (auto e : w->s_ev)
+        if (e) (void)hipEventDestroy(e);
     for (auto e : w->q_ev)
         if (e) (void)hipEventDestroy(e);
     for (auto& p : w->pend) {
@@ -1900,6 +1922,7 @@ int nfk_set_prop_flags(void* world, int32_t c, const uint8_t* flags) {
     World* w = (World*)world;
     if (!w || !flags || c < 0 || c >= w->cfg.n_class) return fail(NFK_ERR_ARG, "bad class");
     for (int p = 0; p < w->n_prop; p++) w->tab.pflags[c][p] = flags[p];
+    w->s_tab_dirty = true;  // (the snapshots' view masks)
     return NFK_OK;
 }
 
@@ -3125,6 +3148,377 @@ int nfk_get_props(void* world, int32_t n, const int64_t* gh, const int64_t* gd, 
         if (pid[i] < 0 || pid[i] >= w->n_if) return fail(NFK_ERR_ARG, "bad property id (object properties: nfk_get_objects)");
     }
     return current_props(w, n, obj.data(), pid, bits);
+}
+
+// ---- enter snapshots (nfk_snapshot_objects): OnPropertyEnter / OnRecordEnter payloads ----
+int nfk_set_snapshot_order(void* world, const int32_t* prop_order, const int32_t* rec_order) {
+    World* w = (World*)world;
+    if (!w) return fail(NFK_ERR_ARG, "null world");
+    auto perm = [](const int32_t* o, int n) {
+        uint8_t seen[kMaxProps] = {};
+        for (int i = 0; i < n; i++) {
+            if (o[i] < 0 || o[i] >= n || seen[o[i]]) return false;
+            seen[o[i]] = 1;
+        }
+        return true;
+    };
+    // (both lists are checked before either is taken)
+    if (prop_order && !perm(prop_order, w->n_prop)) return fail(NFK_ERR_ARG, "prop_order is no permutation of the property ids");
+    if (rec_order && !perm(rec_order, w->cfg.n_rec)) return fail(NFK_ERR_ARG, "rec_order is no permutation of the record ids");
+    w->s_porder.clear();
+    w->s_rorder.clear();
+    if (prop_order) w->s_porder.assign(prop_order, prop_order + w->n_prop);
+    if (rec_order) w->s_rorder.assign(rec_order, rec_order + w->cfg.n_rec);
+    w->s_tab_dirty = true;
+    return NFK_OK;
+}
+
+// the walk table from the flags and the order, on the host and (uploaded) on the device
+static int snap_table(World* w) {
+    if (!w->s_tab_dirty && w->s_tab_d) return NFK_OK;
+    SnapTab& t = w->s_tab;
+    t = SnapTab{};
+    t.n_int = w->cfg.n_int;
+    t.n_if = w->n_if;
+    memset(w->s_cells_ub, 0, sizeof(w->s_cells_ub));
+    for (int pos = 0; pos < w->n_prop; pos++) {
+        const int pid = w->s_porder.empty() ? pos : w->s_porder[pos];
+        t.p_pid[pos] = pid;
+        t.p_off[pos] = w->tab.p_off[pid];
+        for (int c = 0; c < w->cfg.n_class; c++)
+            for (int v = 0; v < 2; v++)
+                if (w->tab.pflags[c][pid] & (v ? NFK_PRIVATE : NFK_PUBLIC)) t.pmask[c][v][pos >> 6] |= 1ull << (pos & 63);
+    }
+    for (int pos = 0; pos < w->cfg.n_rec; pos++) {
+        const int r = w->s_rorder.empty() ? pos : w->s_rorder[pos];
+        SnapRec sr{w->d.rcells[r], w->d.rused[r], r, w->tab.rec_rows[r], w->tab.rec_cols[r], 0};
+        t.rec[pos] = sr;
+        t.rec_of[r] = sr;
+        for (int c = 0; c < w->cfg.n_class; c++)
+            for (int v = 0; v < 2; v++)
+                if (w->tab.rflags[c][r] & (v ? NFK_PRIVATE : NFK_PUBLIC)) {
+                    t.rmask[c][v] |= 1u << pos;
+                    w->s_cells_ub[c][v] += (uint32_t)(sr.rows * sr.cols);
+                }
+    }
+    if (!w->s_tab_d) HIPCHK(hipMalloc((void**)&w->s_tab_d, sizeof(SnapTab)));
+    HIPCHK(hipStreamSynchronize(w->stream));  // (control plane: flags or order changed)
+    HIPCHK(hipMemcpy(w->s_tab_d, &t, sizeof(SnapTab), hipMemcpyHostToDevice));
+    w->s_tab_dirty = false;
+    return NFK_OK;
+}
+
+// the result region's layout for n requests, P property entries, R record entries, C cells
+struct SnapLayout {
+    size_t hdr, p_pid, r_rec, r_cell, p_bits, p_head, r_used, cells, end, r_slot, dev_end;
+    SnapLayout(size_t n, size_t P, size_t R, size_t C, bool heads) {
+        hdr = 0;
+        p_pid = align16(16 * n);
+        r_rec = p_pid + align16(4 * P);
+        r_cell = r_rec + align16(4 * R);
+        p_bits = r_cell + align16(4 * R);
+        p_head = p_bits + align16(8 * P);
+        r_used = p_head + (heads ? align16(8 * P) : 0);
+        cells = r_used + align16(8 * R);
+        end = cells + align16(8 * C);
+        r_slot = end;  // (device only)
+        dev_end = r_slot + align16(4 * R);
+    }
+};
+
+static int snap_pin_reserve(World* w, size_t bytes) {
+    if (bytes <= w->s_pcap) return NFK_OK;
+    if (w->s_pin) HIPCHK(hipHostFree(w->s_pin));
+    w->s_pin = nullptr;
+    const size_t c = std::max(bytes, w->s_pcap + w->s_pcap / 2);
+    w->s_pcap = 0;  // (until the new buffer exists)
+    HIPCHK(hipHostMalloc((void**)&w->s_pin, c, hipHostMallocDefault));
+    w->s_pcap = c;
+    return NFK_OK;
+}
+
+// NFIDataList::IsNullValue of an f64 (NFIDataList.h:160-221), as k_snap tests it
+static bool snap_f64_set_host(uint64_t b) {
+    double v;
+    memcpy(&v, &b, 8);
+    return v > 0.001 || v < -0.001;
+}
+
+// the three count arrays are scanned end to end with int indices: 3 n fits an int (tested before an
+// array of the call is read)
+constexpr int32_t kSnapMaxRequests = INT32_MAX / 3;
+
+// the snapshots of resolved objects (obj[i] < 0: unknown; gh / gd for the message, or null)
+static int snapshot(World* w, int32_t n, const int32_t* obj, const int64_t* gh, const int64_t* gd, const uint8_t* view,
+                    nfk_snapshot* out) {
+    *out = nfk_snapshot{};
+    for (int32_t i = 0; i < n; i++) {
+        if (view[i] != NFK_VIEW_PUBLIC && view[i] != NFK_VIEW_PRIVATE) return fail(NFK_ERR_ARG, "bad view");
+        if (obj[i] < 0)
+            return fail(NFK_ERR_NOTFOUND, gh ? "There is no object " + std::to_string(gh[i]) + "-" + std::to_string(gd[i])
+                                             : "no object index");
+    }
+    if (n == 0) return NFK_OK;
+    if (int r = snap_table(w)) return r;
+    const SnapTab& t = w->s_tab;
+    const bool heads = w->cfg.n_obj > 0;
+
+    // the window's objects with queued Set / record calls (marks set and cleared in this call);
+    // bounds of the totals
+    if (int r = index_queued_sets(w)) return r;
+    if (w->s_mark.size() < (size_t)w->n_obj) w->s_mark.resize(w->n_obj, 0);
+    for (const auto& kv : w->ov_last) w->s_mark[kv.first >> 7] = 1;
+    for (const auto& kv : w->rq_index) w->s_mark[kv.first >> 3] = 1;
+    std::vector<int32_t> host;
+    uint64_t ub_p = 0, ub_r = 0, ub_c = 0;
+    for (int32_t i = 0; i < n; i++) {
+        const int32_t o = obj[i];
+        const int c = w->cls[o], v = view[i] == NFK_VIEW_PRIVATE;
+        ub_p += (uint64_t)(__builtin_popcountll(t.pmask[c][v][0]) + __builtin_popcountll(t.pmask[c][v][1]));
+        ub_r += (uint64_t)__builtin_popcount(t.rmask[c][v]);
+        ub_c += w->s_cells_ub[c][v];
+        if (w->s_mark[o] || w->src_row[o] >= 0) host.push_back(i);
+    }
+    for (const auto& kv : w->ov_last) w->s_mark[kv.first >> 7] = 0;
+    for (const auto& kv : w->rq_index) w->s_mark[kv.first >> 3] = 0;
+    // the totals are bounded from the views alone (every property in view an entry, every row of
+    // every record in view used), before anything is allocated or launched: a batch within the
+    // bound cannot wrap the device's 32-bit counts, so the totals themselves need no second test
+    if (ub_p > 0xFFFFFFFFull || ub_r > 0xFFFFFFFFull || ub_c > 0xFFFFFFFFull)
+        return fail(NFK_ERR_CAPACITY, "snapshot: the bound of the batch's entries or cells does not fit 32 bits");
+    for (int32_t i = 0; i < n; i++)
+        if (w->src_row[obj[i]] < 0 && w->slot_of_obj[obj[i]] < 0) return fail(NFK_ERR_STATE, "object without a slot");
+
+    // ---- the host's answers (read-your-writes): nfk_get_props / nfk_get_objects / nfk_get_records' code
+    std::vector<int32_t> hp_pid, hr_rec;
+    std::vector<uint64_t> hp_bits, hp_head, hr_used, hcells;
+    std::vector<uint32_t> hr_cell, h_np(host.size(), 0), h_nr(host.size(), 0);
+    if (!host.empty()) {
+        std::vector<int32_t> ro, rp, oo, op;
+        for (int32_t i : host) {
+            const int c = w->cls[obj[i]], v = view[i] == NFK_VIEW_PRIVATE;
+            for (int pos = 0; pos < w->n_prop; pos++) {
+                if (!((t.pmask[c][v][pos >> 6] >> (pos & 63)) & 1)) continue;
+                const int pid = t.p_pid[pos];
+                (pid < w->n_if ? ro : oo).push_back(obj[i]);
+                (pid < w->n_if ? rp : op).push_back(pid);
+            }
+        }
+        std::vector<uint64_t> pb(ro.size());
+        std::vector<int64_t> vh(oo.size()), vd(oo.size());
+        if (!ro.empty())
+            if (int r = current_props(w, (int32_t)ro.size(), ro.data(), rp.data(), pb.data())) return r;
+        if (!oo.empty())
+            if (int r = current_objects(w, (int32_t)oo.size(), oo.data(), op.data(), vh.data(), vd.data())) return r;
+        // the records in view: masks in one gather, the used rows' cells of every column in a second
+        struct HEnt { int32_t o, r; const uint64_t* cells; };
+        std::vector<HEnt> ent;
+        std::vector<uint64_t> addr;
+        for (int32_t i : host) {
+            const int c = w->cls[obj[i]], v = view[i] == NFK_VIEW_PRIVATE;
+            for (uint32_t m = t.rmask[c][v]; m; m &= m - 1) {
+                const int r = t.rec[__builtin_ctz(m)].rec;
+                const uint64_t *cells, *used;
+                if (int e = rec_addrs(w, obj[i], r, &cells, &used)) return e;
+                ent.push_back(HEnt{obj[i], r, cells});
+                addr.push_back((uint64_t)(uintptr_t)used);
+            }
+        }
+        std::vector<uint64_t> um(ent.size());
+        if (int e = read_abs(w, addr, um.data())) return e;
+        addr.clear();
+        for (size_t j = 0; j < ent.size(); j++) {
+            const int rows = w->tab.rec_rows[ent[j].r], cols = w->tab.rec_cols[ent[j].r];
+            um[j] &= rec_rowm(rows);
+            const int nu = __builtin_popcountll(um[j]);
+            for (int c = 0; c < cols; c++)
+                for (int p = 0; p < nu; p++) addr.push_back((uint64_t)(uintptr_t)(ent[j].cells + (size_t)c * rows + p));
+        }
+        std::vector<uint64_t> cv(addr.size());
+        if (int e = read_abs(w, addr, cv.data())) return e;
+        size_t ai = 0, oi = 0, ej = 0, ca = 0;
+        for (size_t h = 0; h < host.size(); h++) {
+            const int32_t i = host[h];
+            const int c = w->cls[obj[i]], v = view[i] == NFK_VIEW_PRIVATE;
+            for (int pos = 0; pos < w->n_prop; pos++) {
+                if (!((t.pmask[c][v][pos >> 6] >> (pos & 63)) & 1)) continue;
+                const int pid = t.p_pid[pos];
+                uint64_t bits, head = 0;
+                bool keep;
+                if (pid < w->n_if) {
+                    bits = pb[ai++];
+                    keep = pid < w->cfg.n_int ? bits != 0 : snap_f64_set_host(bits);
+                } else {
+                    bits = (uint64_t)vd[oi];
+                    head = (uint64_t)vh[oi++];
+                    keep = (bits | head) != 0;
+                }
+                if (!keep) continue;
+                hp_pid.push_back(pid);
+                hp_bits.push_back(bits);
+                hp_head.push_back(head);
+                h_np[h]++;
+            }
+            for (uint32_t m = t.rmask[c][v]; m; m &= m - 1, ej++) {
+                const int r = ent[ej].r, rows = w->tab.rec_rows[r], cols = w->tab.rec_cols[r];
+                const int nu = __builtin_popcountll(um[ej]);
+                uint64_t u_now = um[ej];
+                hr_rec.push_back(r);
+                hr_cell.push_back((uint32_t)hcells.size());
+                for (int col = 0; col < cols; col++) {
+                    uint64_t u = um[ej], cr[64] = {};
+                    for (int row = 0, p = 0; row < rows; row++)
+                        if ((u >> row) & 1) cr[row] = cv[ca + (size_t)col * nu + p++];  // (used rows first: rec_pos)
+                    replay_column(w, ent[ej].o, r, col, u, cr);
+                    u_now = u;
+                    for (int row = 0; row < rows; row++)
+                        if ((u >> row) & 1) hcells.push_back(cr[row]);
+                }
+                ca += (size_t)cols * nu;
+                hr_used.push_back(u_now);
+                h_nr[h]++;
+            }
+        }
+    }
+    out->n_host = (int32_t)host.size();
+
+    // ---- the kernels' answers: every request keeps its place in the batch, a host request as slot -1
+    const size_t nn = (size_t)n;
+    const size_t o_tot = align16(8 * nn), o_res = o_tot + 16;  // pinned: requests, the three totals, the result
+    uint32_t Pd = 0, Rd = 0, Cd = 0;
+    const bool launch = host.size() < nn;
+    const size_t a_req = 0, a_cnt = align16(8 * nn), a_base = a_cnt + align16(12 * nn), a_tot = a_base + align16(12 * nn + 4),
+                 a_end = a_tot + 16;
+    char* A = nullptr;
+    const bool timed = w->profiling && launch;
+    if (launch) {
+        if (int r = snap_pin_reserve(w, o_res + SnapLayout(nn, 0, 0, 0, heads).end)) return r;
+        if (int r = dev_reserve(w, &w->s_dev, &w->s_dcap, a_end)) return r;
+        A = (char*)w->s_dev;
+        SnapReq* hq = (SnapReq*)w->s_pin;
+        for (int32_t i = 0; i < n; i++) hq[i] = SnapReq{w->slot_of_obj[obj[i]], view[i] == NFK_VIEW_PRIVATE ? 1u : 0u};
+        for (int32_t i : host) hq[i].slot = -1;
+        if (timed)
+            for (auto& e : w->s_ev)
+                if (!e) HIPCHK(hipEventCreate(&e));
+        HIPCHK(hipMemcpyAsync(A + a_req, hq, 8 * nn, hipMemcpyHostToDevice, w->stream));
+        if (timed) HIPCHK(hipEventRecord(w->s_ev[0], w->stream));
+        hipLaunchKernelGGL(k_snap<false>, dim3((unsigned)((nn + kTPB - 1) / kTPB)), dim3(kTPB), 0, w->stream,
+                           (const SnapTab*)w->s_tab_d, (const uint64_t*)w->d.pmem, w->d.fan_desc,
+                           (const SnapReq*)(A + a_req), n, (uint32_t*)(A + a_cnt), (const uint32_t*)nullptr,
+                           (uint32_t*)nullptr, (int32_t*)nullptr, (uint64_t*)nullptr, (uint64_t*)nullptr,
+                           (int32_t*)nullptr, (uint64_t*)nullptr, (uint32_t*)nullptr, (int32_t*)nullptr, 0u, 0u);
+        hipLaunchKernelGGL(k_snap_scan, dim3(1), dim3(1024), 0, w->stream, (const uint32_t*)(A + a_cnt),
+                           (uint32_t*)(A + a_base), (int)(3 * n), n, (uint32_t*)(A + a_tot));
+        HIPCHK(hipGetLastError());
+        if (timed) HIPCHK(hipEventRecord(w->s_ev[1], w->stream));
+        uint32_t* tot = (uint32_t*)(w->s_pin + o_tot);
+        HIPCHK(hipMemcpyAsync(tot, A + a_tot, 12, hipMemcpyDeviceToHost, w->stream));
+        HIPCHK(hipStreamSynchronize(w->stream));
+        Pd = tot[0];
+        Rd = tot[1] - tot[0];
+        Cd = tot[2] - tot[1];
+        // (an invariant, not a state a batch can reach: the counts are sums of what the bounds bound)
+        if (Pd > ub_p || Rd > ub_r || Cd > ub_c) return fail(NFK_ERR_DEVICE, "snapshot: more entries than the views hold");
+    }
+    const uint64_t P = (uint64_t)Pd + hp_pid.size(), R = (uint64_t)Rd + hr_rec.size(), C = (uint64_t)Cd + hcells.size();
+    const SnapLayout L(nn, (size_t)P, (size_t)R, (size_t)C, heads);
+    if (int r = snap_pin_reserve(w, o_res + L.end)) return r;  // (the requests are on the device by now)
+    char* H = w->s_pin + o_res;
+    if (launch) {
+        if (int r = dev_reserve(w, &w->s_out, &w->s_ocap, L.dev_end)) return r;
+        char* B = (char*)w->s_out;
+        if (timed) HIPCHK(hipEventRecord(w->s_ev[2], w->stream));
+        hipLaunchKernelGGL(k_snap<true>, dim3((unsigned)((nn + kTPB - 1) / kTPB)), dim3(kTPB), 0, w->stream,
+                           (const SnapTab*)w->s_tab_d, (const uint64_t*)w->d.pmem, w->d.fan_desc,
+                           (const SnapReq*)(A + a_req), n, (uint32_t*)nullptr, (const uint32_t*)(A + a_base),
+                           (uint32_t*)(B + L.hdr), (int32_t*)(B + L.p_pid), (uint64_t*)(B + L.p_bits),
+                           heads ? (uint64_t*)(B + L.p_head) : (uint64_t*)nullptr, (int32_t*)(B + L.r_rec),
+                           (uint64_t*)(B + L.r_used), (uint32_t*)(B + L.r_cell), (int32_t*)(B + L.r_slot), Pd, Rd);
+        if (Rd && Cd) {
+            const uint64_t blocks = ((uint64_t)Rd * 64 + kTPB - 1) / kTPB;
+            hipLaunchKernelGGL(k_snap_cells, dim3((unsigned)blocks), dim3(kTPB), 0, w->stream, (const SnapTab*)w->s_tab_d,
+                               (const int32_t*)(B + L.r_rec), (const int32_t*)(B + L.r_slot),
+                               (const uint64_t*)(B + L.r_used), (const uint32_t*)(B + L.r_cell), Rd,
+                               (uint64_t*)(B + L.cells), Cd);
+        }
+        HIPCHK(hipGetLastError());
+        if (timed) HIPCHK(hipEventRecord(w->s_ev[3], w->stream));
+        HIPCHK(hipMemcpyAsync(H, B, L.end, hipMemcpyDeviceToHost, w->stream));
+        HIPCHK(hipStreamSynchronize(w->stream));
+        out->bytes = (int64_t)L.end;
+        if (timed) {
+            float m0 = 0, m1 = 0;
+            HIPCHK(hipEventElapsedTime(&m0, w->s_ev[0], w->s_ev[1]));
+            HIPCHK(hipEventElapsedTime(&m1, w->s_ev[2], w->s_ev[3]));
+            out->kernel_ms = (double)m0 + (double)m1;
+        }
+    }
+    uint32_t* hdr = (uint32_t*)(H + L.hdr);
+    int32_t* p_pid = (int32_t*)(H + L.p_pid);
+    uint64_t* p_bits = (uint64_t*)(H + L.p_bits);
+    uint64_t* p_head = heads ? (uint64_t*)(H + L.p_head) : nullptr;
+    int32_t* r_rec = (int32_t*)(H + L.r_rec);
+    uint64_t* r_used = (uint64_t*)(H + L.r_used);
+    uint32_t* r_cell = (uint32_t*)(H + L.r_cell);
+    uint64_t* cells = (uint64_t*)(H + L.cells);
+    // the host's runs behind the kernels': nothing is moved
+    uint32_t pa = Pd, ra = Rd;
+    for (size_t h = 0; h < host.size(); h++) {
+        const size_t i = (size_t)host[h];
+        hdr[i] = pa;
+        hdr[nn + i] = h_np[h];
+        hdr[2 * nn + i] = ra;
+        hdr[3 * nn + i] = h_nr[h];
+        pa += h_np[h];
+        ra += h_nr[h];
+    }
+    for (size_t k = 0; k < hp_pid.size(); k++) {
+        p_pid[Pd + k] = hp_pid[k];
+        p_bits[Pd + k] = hp_bits[k];
+        if (p_head) p_head[Pd + k] = hp_head[k];
+    }
+    for (size_t k = 0; k < hr_rec.size(); k++) {
+        r_rec[Rd + k] = hr_rec[k];
+        r_used[Rd + k] = hr_used[k];
+        r_cell[Rd + k] = Cd + hr_cell[k];
+    }
+    if (!hcells.empty()) memcpy(cells + Cd, hcells.data(), hcells.size() * 8);
+    out->p_first = hdr;
+    out->p_count = hdr + nn;
+    out->r_first = hdr + 2 * nn;
+    out->r_count = hdr + 3 * nn;
+    out->p_pid = p_pid;
+    out->p_bits = p_bits;
+    out->p_head = p_head;
+    out->r_rec = r_rec;
+    out->r_used = r_used;
+    out->r_cell = r_cell;
+    out->cells = cells;
+    return NFK_OK;
+}
+
+int nfk_snapshot_objects(void* world, int32_t n, const int64_t* gh, const int64_t* gd, const uint8_t* view,
+                         nfk_snapshot* out) {
+    World* w = (World*)world;
+    if (!w) return fail(NFK_ERR_ARG, "null world");
+    if (!out || n < 0 || (n && (!gh || !gd || !view))) return fail(NFK_ERR_ARG, "null argument");
+    if (!w->committed) return fail(NFK_ERR_STATE, "commit first");
+    if (n > kSnapMaxRequests) return fail(NFK_ERR_CAPACITY, "snapshot: too many requests in one batch");
+    std::vector<int32_t> obj(n);
+    if (int rl = find_many_par(w, n, gh, gd, obj.data())) return rl;
+    return snapshot(w, n, obj.data(), gh, gd, view, out);
+}
+
+int nfk_snapshot_objects_obj(void* world, int32_t n, const int32_t* obj, const uint8_t* view, nfk_snapshot* out) {
+    World* w = (World*)world;
+    if (!w) return fail(NFK_ERR_ARG, "null world");
+    if (!out || n < 0 || (n && (!obj || !view))) return fail(NFK_ERR_ARG, "null argument");
+    if (!w->committed) return fail(NFK_ERR_STATE, "commit first");
+    if (n > kSnapMaxRequests) return fail(NFK_ERR_CAPACITY, "snapshot: too many requests in one batch");
+    const int32_t* lo = live_objects(w, n, obj);
+    const std::vector<int32_t> o(lo, lo + n);  // (w->look is the lookups' scratch)
+    return snapshot(w, n, o.data(), nullptr, nullptr, view, out);
 }
 
 int nfk_exist_schedule(void* world, int64_t gh, int64_t gd, int32_t kind, int32_t* exists) {

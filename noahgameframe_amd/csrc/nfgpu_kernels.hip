@@ -2407,4 +2407,166 @@ __global__ __launch_bounds__(kTPB) void k_find_rows(const FindDev* __restrict__ 
     if (q < n && row == 0) masks[q] = (b >> (lane - row)) & rec_rowm(G);
 }
 
+// ---------------------------------------------------------------------------------
+// Enter snapshots (nfk_snapshot_objects): what NFCGameServerNet_ServerModule::OnPropertyEnter /
+// OnRecordEnter pack for a batch of (object, view) requests.  The walk is a table (SnapTab, built
+// by the host whenever flags or the walk's order change): the properties by ORDER POSITION (the
+// caller's name order) and per (class, view) a 128-bit mask over the positions in view, the same
+// for the records.  k_snap<false> counts a request's property entries, record entries and cells
+// (one thread per request), k_snap_scan (k_scan_counts' form) scans the three count arrays laid end to end,
+// k_snap<true> evaluates the same predicates and writes the entries at the scanned places, and
+// k_snap_cells copies each record entry's used rows (one wave per entry).  A place comes from the
+// request's position alone: no atomic, no LDS (but the scan's chunk sums), no workgroup waits on another.
+struct SnapRec {
+    const uint64_t* cells;  // Dev::rcells / rused of the record at this order position
+    const uint64_t* used;
+    int32_t rec, rows, cols, pad;
+};
+struct SnapTab {
+    int64_t p_off[kMaxProps];  // by order position: Tables::p_off / the property id
+    int32_t p_pid[kMaxProps];
+    uint64_t pmask[NFK_MAX_CLASSES][2][2];  // [class][view: 0 public, 1 private][word]: positions in view
+    uint32_t rmask[NFK_MAX_CLASSES][2];     // the same over the records' order positions
+    SnapRec rec[NFK_MAX_RECORDS];           // by order position
+    SnapRec rec_of[NFK_MAX_RECORDS];        // by record id (k_snap_cells)
+    int32_t n_int, n_if, pad0, pad1;
+};
+struct SnapReq {
+    int32_t slot;   // -1: answered on the host (counts 0)
+    uint32_t view;  // 0 public, 1 private
+};
+// NFIDataList::IsNullValue (NFIDataList.h:160-221) of an f64: the two ordered compares, so a NaN
+// is null (not packed); not fabs
+__device__ __forceinline__ bool snap_f64_set(uint64_t b) {
+    const double v = __longlong_as_double((long long)b);
+    return v > 0.001 || v < -0.001;
+}
+template <bool kWrite>
+__global__ __launch_bounds__(kTPB) void k_snap(const SnapTab* __restrict__ tab, const uint64_t* __restrict__ pmem,
+                                               const uint64_t* __restrict__ fan_desc, const SnapReq* __restrict__ req,
+                                               int32_t n, uint32_t* __restrict__ cnt, const uint32_t* __restrict__ base,
+                                               uint32_t* __restrict__ hdr, int32_t* __restrict__ p_pid, uint64_t* __restrict__ p_bits,
+                                               uint64_t* __restrict__ p_head, int32_t* __restrict__ r_rec,
+                                               uint64_t* __restrict__ r_used, uint32_t* __restrict__ r_cell,
+                                               int32_t* __restrict__ r_slot, uint32_t p_cap, uint32_t r_cap) {
+    const int64_t i = (int64_t)blockIdx.x * kTPB + threadIdx.x;
+    if (i >= n) return;
+    const SnapReq rq = req[i];
+    uint32_t np = 0, nr = 0, nc = 0, pb = 0, rb = 0, cb = 0;
+    if constexpr (kWrite) {
+        pb = base[i];
+        rb = base[(int64_t)n + i] - base[n];
+        cb = base[2 * (int64_t)n + i] - base[2 * (int64_t)n];
+    }
+    const uint32_t cls = rq.slot >= 0 ? (uint32_t)(fan_desc[rq.slot] >> 60) : 0xFu;
+    // (a slack slot is never reached: the host checks the object first.  The p_cap / r_cap tests
+    // below and k_snap_cells' c_cap keep a store inside the result buffers whatever the two passes
+    // read; they evaluate the same predicates on the same memory, so the tests never fail.)
+    if (cls != 0xFu) {
+        const int64_t slot = rq.slot;
+        const uint32_t v = rq.view & 1u;
+        const int n_int = tab->n_int, n_if = tab->n_if;
+        for (int wd = 0; wd < 2; wd++)
+            for (uint64_t m = tab->pmask[cls][v][wd]; m; m &= m - 1) {
+                const int pos = wd * 64 + __builtin_ctzll(m);
+                const int pid = tab->p_pid[pos];
+                const uint64_t* p = pmem + tab->p_off[pos];
+                uint64_t bits, head = 0;
+                bool keep;
+                if (pid < n_int) {
+                    bits = p[slot];
+                    keep = bits != 0;
+                } else if (pid < n_if) {
+                    bits = p[slot];
+                    keep = snap_f64_set(bits);
+                } else {
+                    bits = p[2 * slot];  // (data, head)
+                    head = p[2 * slot + 1];
+                    keep = (bits | head) != 0;
+                }
+                if (!keep) continue;
+                if constexpr (kWrite) {
+                    const uint32_t at = pb + np;
+                    if (at < p_cap) {
+                        p_pid[at] = pid;
+                        p_bits[at] = bits;
+                        if (p_head) p_head[at] = head;
+                    }
+                }
+                np++;
+            }
+        for (uint32_t m = tab->rmask[cls][v]; m; m &= m - 1) {
+            const SnapRec& sr = tab->rec[__builtin_ctz(m)];
+            const uint64_t used = sr.used[slot] & rec_rowm(sr.rows);
+            if constexpr (kWrite) {
+                const uint32_t at = rb + nr;
+                if (at < r_cap) {
+                    r_rec[at] = sr.rec;
+                    r_used[at] = used;
+                    r_cell[at] = cb + nc;
+                    r_slot[at] = rq.slot;
+                }
+            }
+            nr++;
+            nc += (uint32_t)sr.cols * (uint32_t)__builtin_popcountll(used);
+        }
+    }
+    if constexpr (!kWrite) {
+        cnt[i] = np;
+        cnt[(int64_t)n + i] = nr;
+        cnt[2 * (int64_t)n + i] = nc;
+    } else {  // hdr [4][n]: p_first, p_count, r_first, r_count
+        hdr[i] = pb;
+        hdr[(int64_t)n + i] = np;
+        hdr[2 * (int64_t)n + i] = rb;
+        hdr[3 * (int64_t)n + i] = nr;
+    }
+}
+// k_scan_counts over the 3 n counts (request counts of property entries, record entries, cells, end
+// to end), and the three totals tot[k] = out[(k + 1) n] side by side, so one 12-byte copy reads them
+__global__ __launch_bounds__(1024) void k_snap_scan(const uint32_t* __restrict__ cnt, uint32_t* __restrict__ out, int n3,
+                                                    int n, uint32_t* __restrict__ tot) {
+    __shared__ uint32_t s[1024];
+    const int per = (n3 + 1023) / 1024, i0 = min(n3, (int)threadIdx.x * per), i1 = min(n3, i0 + per);
+    uint32_t sum = 0;
+    for (int i = i0; i < i1; i++) sum += cnt[i];
+    s[threadIdx.x] = sum;
+    __syncthreads();
+    for (int o = 1; o < 1024; o <<= 1) {
+        const uint32_t v = threadIdx.x >= (unsigned)o ? s[threadIdx.x - o] : 0u;
+        __syncthreads();
+        s[threadIdx.x] += v;
+        __syncthreads();
+    }
+    uint32_t acc = s[threadIdx.x] - sum;
+    for (int i = i0; i < i1; i++) {
+        out[i] = acc;
+        acc += cnt[i];
+    }
+    if (threadIdx.x == 1023) out[n3] = s[1023];
+    __syncthreads();  // (out: this workgroup's own global stores)
+    if (threadIdx.x < 3) tot[threadIdx.x] = out[(int64_t)(threadIdx.x + 1) * n];
+}
+// one wave per record entry: its cols x popcount(used) cells are one dense run of the output (column
+// c's used rows at r_cell + c * n_used) and cols dense runs of the slot's column vectors (the used
+// rows come first: rec_pos); a lane takes every 64th cell of the entry
+__global__ __launch_bounds__(kTPB) void k_snap_cells(const SnapTab* __restrict__ tab, const int32_t* __restrict__ r_rec,
+                                                     const int32_t* __restrict__ r_slot,
+                                                     const uint64_t* __restrict__ r_used,
+                                                     const uint32_t* __restrict__ r_cell, uint32_t n_ent,
+                                                     uint64_t* __restrict__ cells, uint32_t c_cap) {
+    const int64_t e = ((int64_t)blockIdx.x * kTPB + threadIdx.x) >> 6;
+    if (e >= (int64_t)n_ent) return;
+    const int lane = (int)(threadIdx.x & 63);
+    const SnapRec& sr = tab->rec_of[r_rec[e] & (NFK_MAX_RECORDS - 1)];
+    const uint32_t nu = (uint32_t)__builtin_popcountll(r_used[e] & rec_rowm(sr.rows));
+    if (nu == 0) return;
+    const uint64_t* src = sr.cells + (size_t)r_slot[e] * sr.cols * sr.rows;
+    const uint32_t tot = nu * (uint32_t)sr.cols, at = r_cell[e];
+    for (uint32_t x = (uint32_t)lane; x < tot; x += 64) {
+        const uint32_t c = x / nu, k = x - c * nu;
+        if (at + x < c_cap) cells[at + x] = src[(size_t)c * sr.rows + k];
+    }
+}
+
 }  // namespace nfgpu

@@ -11,6 +11,8 @@
 
 namespace nfgpu {
 
+static void* nfgpu_symbol(const char* name);  // (below: an entry point of the loaded nfgpu library, or null)
+
 static uint64_t bits_of(double d) { uint64_t u; std::memcpy(&u, &d, 8); return u; }
 static double dbl_of(uint64_t u) { double d; std::memcpy(&d, &u, 8); return d; }
 
@@ -338,6 +340,21 @@ bool NFGPUKernelModule::AfterInit() {
     }
     rec_init_.clear();
     check(nfk_commit(world_), "nfk_commit");
+    {
+        // the enter views' walk: device properties and records by name, byte-wise (the reference's
+        // std::map<std::string, ...> First / Next); resolved at first use like the queries' entry points
+        using Fn = int (*)(void*, const int32_t*, const int32_t*);
+        if (Fn fn = (Fn)nfgpu_symbol("nfk_set_snapshot_order")) {
+            std::vector<int32_t> po, ro;
+            std::vector<std::pair<std::string, int32_t>> by_name;
+            for (auto& pd : props_) by_name.push_back({pd.name, PropertyId(pd.name)});
+            std::sort(by_name.begin(), by_name.end());
+            for (auto& kv : by_name) po.push_back(kv.second);
+            for (int r = 0; r < (int)records_.size(); r++) ro.push_back(r);
+            std::sort(ro.begin(), ro.end(), [&](int32_t a, int32_t b) { return records_[a].name < records_[b].name; });
+            check(fn(world_, po.empty() ? nullptr : po.data(), ro.empty() ? nullptr : ro.data()), "nfk_set_snapshot_order");
+        }
+    }
     {
         auto pid_of = [&](const char* nm, TDATA_TYPE t) {
             auto it = prop_id_.find(nm);
@@ -930,6 +947,91 @@ void NFGPUKernelModule::FindRows(const std::vector<RowFind>& finds, std::vector<
     check(fn(world_, (int32_t)at.size(), gh.data(), gd.data(), rec.data(), col.data(), bits.data(), m.data()),
           "nfk_find_rows");
     for (size_t j = 0; j < at.size(); j++) hits[at[j]].mask = m[j];
+}
+
+// ---- enter views (NFCGameServerNet_ServerModule.cpp:271-554) ----
+void NFGPUKernelModule::GetEnterViews(const std::vector<NFGUID>& objects, const std::vector<uint8_t>& bPrivate,
+                                      std::vector<EnterView>& out) {
+    using Fn = int (*)(void*, int32_t, const int32_t*, const uint8_t*, nfk_snapshot*);
+    static const Fn fn = (Fn)nfgpu_symbol("nfk_snapshot_objects_obj");
+    if (!fn) throw std::runtime_error("nfk_snapshot_objects_obj: the nfgpu library has no such entry point");
+    Flush();  // (the buffered Set calls first: call order)
+    out.assign(objects.size(), EnterView{});
+    std::vector<int32_t> obj;
+    std::vector<uint8_t> view;
+    std::vector<size_t> at;
+    for (size_t i = 0; i < objects.size(); i++) {
+        out[i].bPrivate = i < bPrivate.size() && bPrivate[i] != 0;
+        const int o = committed_ ? ObjectIndex(objects[i]) : -1;
+        if (o < 0) continue;  // (self stays null)
+        out[i].self = objects[i];
+        obj.push_back(o);
+        view.push_back(out[i].bPrivate ? NFK_VIEW_PRIVATE : NFK_VIEW_PUBLIC);
+        at.push_back(i);
+    }
+    if (at.empty()) return;
+    nfk_snapshot s{};
+    check(fn(world_, (int32_t)at.size(), obj.data(), view.data(), &s), "nfk_snapshot_objects_obj");
+    for (size_t j = 0; j < at.size(); j++) {
+        EnterView& v = out[at[j]];
+        v.properties.reserve(s.p_count[j]);
+        for (uint32_t e = s.p_first[j]; e < s.p_first[j] + s.p_count[j]; e++) {
+            const PropertyDef& pd = props_[(size_t)def_of_pid_[(size_t)s.p_pid[e]]];
+            TData d;
+            d.type = pd.type;
+            if (pd.type == TDATA_INT) d.i = (int64_t)s.p_bits[e];
+            else if (pd.type == TDATA_FLOAT) memcpy(&d.f, &s.p_bits[e], 8);
+            else d.o = NFGUID((int64_t)(s.p_head ? s.p_head[e] : 0), (int64_t)s.p_bits[e]);
+            v.properties.push_back(EnterProperty{&pd.name, d});
+        }
+        v.records.reserve(s.r_count[j]);
+        for (uint32_t e = s.r_first[j]; e < s.r_first[j] + s.r_count[j]; e++) {
+            const RecordDef& rd = records_[(size_t)s.r_rec[e]];
+            EnterRecord er{&rd.name, s.r_used[e], {}};
+            const size_t nu = (size_t)__builtin_popcountll(s.r_used[e]), nc = rd.cols.size();
+            er.cells.resize(nu * nc);
+            for (size_t k = 0; k < nu; k++)      // the device's column-major run as the reference's rows
+                for (size_t c = 0; c < nc; c++) {
+                    const uint64_t b = s.cells[(size_t)s.r_cell[e] + c * nu + k];
+                    TData& d = er.cells[k * nc + c];
+                    d.type = rd.cols[c];
+                    if (d.type == TDATA_INT) d.i = (int64_t)b;
+                    else memcpy(&d.f, &b, 8);
+                }
+            v.records.push_back(std::move(er));
+        }
+    }
+}
+
+bool NFGPUKernelModule::GetGroupEnterViews(const NFGUID& self, int nSceneID, int nGroupID,
+                                           std::vector<NFGUID>& playersNoSelf, std::vector<NFGUID>& objectsNoSelf,
+                                           std::vector<EnterView>& out) {
+    using Fn = int (*)(void*, int32_t, const nfk_query*, nfk_query_result*);
+    static const Fn fn = (Fn)nfgpu_symbol("nfk_query_objects");
+    if (!fn) throw std::runtime_error("nfk_query_objects: the nfgpu library has no such entry point");
+    playersNoSelf.clear();
+    objectsNoSelf.clear();
+    out.clear();
+    if (!committed_) return false;
+    Flush();
+    nfk_query q[2] = {};
+    for (int i = 0; i < 2; i++) {  // players then others (KM:1169), both without self (AOI:396-455)
+        q[i].scene = nSceneID;
+        q[i].group = nGroupID;
+        q[i].who = i == 0 ? NFK_Q_PLAYERS : NFK_Q_OTHERS;
+        q[i].cls_mask = 0x7FFFu;
+        q[i].pid = -1;
+        q[i].skip_obj = ObjectIndex(self);
+    }
+    nfk_query_result r{};
+    check(fn(world_, 2, q, &r), "nfk_query_objects");
+    if (!r.exists[0]) return false;
+    for (uint32_t i = r.off[0]; i < r.off[1]; i++) playersNoSelf.push_back(guids_[(size_t)r.obj[i]]);
+    for (uint32_t i = r.off[0]; i < r.off[2]; i++) objectsNoSelf.push_back(guids_[(size_t)r.obj[i]]);
+    std::vector<NFGUID> want(objectsNoSelf);
+    want.push_back(self);
+    GetEnterViews(want, std::vector<uint8_t>(want.size(), 0), out);
+    return true;
 }
 
 static int append_rows(const NFGPUKernelModule::RowHits& h, std::vector<int>& varResult) {

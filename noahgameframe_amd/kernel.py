@@ -70,6 +70,16 @@ class QueryResult(ctypes.Structure):
                 ("bytes", ctypes.c_int64)]
 
 
+class Snapshot(ctypes.Structure):
+    _U32, _I32, _U64 = ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_uint64)
+    _fields_ = [("p_first", _U32), ("p_count", _U32), ("p_pid", _I32), ("p_bits", _U64), ("p_head", _U64),
+                ("r_first", _U32), ("r_count", _U32), ("r_rec", _I32), ("r_used", _U64), ("r_cell", _U32),
+                ("cells", _U64), ("kernel_ms", ctypes.c_double), ("bytes", ctypes.c_int64),
+                ("n_host", ctypes.c_int32)]
+
+
+VIEW_PUBLIC, VIEW_PRIVATE = 1, 2
+MAX_RECORDS = 8   # NFK_MAX_RECORDS
 Q_PLAYERS, Q_OTHERS = 0, 1
 Q_ALL_GROUPS = 1
 Q_INT_EQ32, Q_OBJ_EQ = 0, 1
@@ -132,6 +142,8 @@ def load_library(path=LIB_PATH):
         "nfk_query_objects": [VP, I32, VP, P(QueryResult)], "nfk_online_count": [VP, I32, I32, VP],
         "nfk_find_rows": [VP, I32, VP, VP, VP, VP, VP, VP], "nfk_find_rows_obj": [VP, I32, VP, VP, VP, VP, VP],
         "nfk_find_stats": [VP, VP, VP, VP], "nfk_get_used_rows": [VP, I32, VP, VP, VP, VP],
+        "nfk_snapshot_objects": [VP, I32, VP, VP, VP, P(Snapshot)],
+        "nfk_snapshot_objects_obj": [VP, I32, VP, VP, P(Snapshot)], "nfk_set_snapshot_order": [VP, VP, VP],
     }
     for name, args in sig.items():
         if not hasattr(lib, name) and os.environ.get("NFGPU_LIB"):
@@ -368,6 +380,58 @@ class NFKernelModule:
             return None
         cols = shape[0]
         return self.get_records([guid[0]] * cols, [guid[1]] * cols, [rec] * cols, [row] * cols, list(range(cols)))
+
+    # ---- enter snapshots: OnPropertyEnter / OnRecordEnter payloads (nfk_snapshot_objects) ----
+    def set_snapshot_order(self, prop_order=None, rec_order=None):
+        """nfk_set_snapshot_order: the walk's order as permutations of the property ids and of the
+        record ids (the reference walks its maps by name); None: id order"""
+        po = None if prop_order is None else np.ascontiguousarray(prop_order, np.int32)
+        ro = None if rec_order is None else np.ascontiguousarray(rec_order, np.int32)
+        if po is not None and len(po) != self.n_int + self.n_flt + self.n_oprops:
+            raise NFKError(-1, "prop_order: one entry per property")
+        if ro is not None and len(ro) != self.n_rec:
+            raise NFKError(-1, "rec_order: one entry per record")
+        self._chk(self.lib.nfk_set_snapshot_order(self.h, _p(po), _p(ro)))
+
+    def _snapshot_arrays(self, res, n, stats):
+        def arr(ptr, k, dt):
+            return np.ctypeslib.as_array(ptr, (k,)).copy() if k else np.zeros(0, dt)
+        out = {k: arr(getattr(res, k), n, np.uint32) for k in ("p_first", "p_count", "r_first", "r_count")}
+        n_p = int((out["p_first"].astype(np.int64) + out["p_count"]).max()) if n else 0
+        n_r = int((out["r_first"].astype(np.int64) + out["r_count"]).max()) if n else 0
+        out["p_pid"] = arr(res.p_pid, n_p, np.int32)
+        out["p_bits"] = arr(res.p_bits, n_p, np.uint64)
+        out["p_head"] = arr(res.p_head, n_p, np.uint64) if res.p_head else None
+        out["r_rec"] = arr(res.r_rec, n_r, np.int32)
+        out["r_used"] = arr(res.r_used, n_r, np.uint64)
+        out["r_cell"] = arr(res.r_cell, n_r, np.uint32)
+        # the entries' used-row counts (one byte-table pass), and from them the cells' extent
+        out["r_nused"] = np.unpackbits(out["r_used"].view(np.uint8)).reshape(n_r, 64).sum(1, dtype=np.int64)
+        cols = np.array([self.rec_shape.get(r, (0, 0))[0] for r in range(MAX_RECORDS)], np.int64)
+        n_c = int((out["r_cell"].astype(np.int64) + cols[out["r_rec"]] * out["r_nused"]).max()) if n_r else 0
+        out["cells"] = arr(res.cells, n_c, np.uint64)
+        if stats is not None:
+            stats["kernel_ms"], stats["bytes"], stats["n_host"] = res.kernel_ms, res.bytes, res.n_host
+        return out
+
+    def snapshot_objects(self, guid_head, guid_data, view, stats=None):
+        """nfk_snapshot_objects: n (object, view) requests (VIEW_PUBLIC / VIEW_PRIVATE) -> a dict of
+        numpy copies of the nfk_snapshot arrays (p_first, p_count, p_pid, p_bits, p_head or None,
+        r_first, r_count, r_rec, r_used, r_cell, cells; r_nused: the entries' used-row counts), the
+        reference's now.  stats: a dict that receives kernel_ms (with set_profiling(True)), the bytes
+        read back and the requests answered on the host (n_host)."""
+        gh, gd = np.ascontiguousarray(guid_head, np.int64), np.ascontiguousarray(guid_data, np.int64)
+        v = np.ascontiguousarray(view, np.uint8)
+        res = Snapshot()
+        self._chk(self.lib.nfk_snapshot_objects(self.h, len(gh), _p(gh), _p(gd), _p(v), ctypes.byref(res)))
+        return self._snapshot_arrays(res, len(gh), stats)
+
+    def snapshot_objects_obj(self, obj, view, stats=None):
+        """nfk_snapshot_objects_obj: snapshot_objects by object index (query_objects' hits, ev_obj)"""
+        o, v = np.ascontiguousarray(obj, np.int32), np.ascontiguousarray(view, np.uint8)
+        res = Snapshot()
+        self._chk(self.lib.nfk_snapshot_objects_obj(self.h, len(o), _p(o), _p(v), ctypes.byref(res)))
+        return self._snapshot_arrays(res, len(o), stats)
 
     def SetRecordInt(self, guid, rec, row, col, value):
         self.set_records([guid[0]], [guid[1]], [rec], [row], [col], [np.int64(value).view(np.uint64)], [0])
