@@ -40,6 +40,13 @@
 //     are resolved; on the C-ABI nfk_define_record of it comes before nfk_define_kind.
 //   * String / Vector properties stay host-side (not on the frame path); object (NFGUID) properties
 //     are device columns like the int / float ones.
+//   * Records hold int, float and object (NFGUID) columns (AddRecord: TDATA_OBJECT); string and vector
+//     columns do not exist on the device.  An object column is two physical columns there (its data
+//     half, then its head half; at most 16 physical columns per record): the record calls here —
+//     SetRecordObject, GetRecordObject, FindObject, FindRowByColValue, QueryRow, AddRow, the enter
+//     views' cells and the record callbacks' nCol — speak the reference's logical columns and carry an
+//     object cell as one TDATA_OBJECT; heartbeat programs name physical columns.  No heartbeat op or
+//     guard works on an object cell.
 //   * An enter view (GetEnterViews / GetGroupEnterViews: the OnPropertyEnter / OnRecordEnter payload)
 //     holds the device properties and records only: host-side string and vector properties are NOT
 //     in it, the host packs them itself.
@@ -319,7 +326,15 @@ public:
         std::map<std::string, uint8_t> prop_flags;   // NFK_PUBLIC | NFK_PRIVATE | NFK_UPLOAD
         std::map<std::string, uint8_t> record_flags;
     };
-    struct RecordDef { std::string name; int rows; std::vector<TDATA_TYPE> cols; };
+    // cols: the reference's LOGICAL columns.  On the device an object (NFGUID) column is two adjacent
+    // physical columns, data half then head half (nfgpu.h NFK_REC_OBJ_DATA / NFK_REC_OBJ_HEAD): phys[c]
+    // is logical column c's physical column (an object's: its data half), logical[p] the logical column
+    // of physical column p, pcols the physical count (<= NFK_MAX_REC_COLS)
+    struct RecordDef {
+        std::string name; int rows; std::vector<TDATA_TYPE> cols;
+        std::vector<int> phys, logical;
+        int pcols = 0;
+    };
     struct HeartBeatDef {
         std::string name;
         std::vector<nfk_op> ops;
@@ -333,6 +348,10 @@ public:
     int AddProperty(const std::string& name, TDATA_TYPE type);  // TDATA_INT / FLOAT / OBJECT; returns its index
     int AddClass(const std::string& name);
     void SetPropertyFlags(const std::string& cls, const std::string& prop, bool pub, bool priv, bool upload);
+    // cols: TDATA_INT / TDATA_FLOAT / TDATA_OBJECT per logical column; throws std::invalid_argument when
+    // the physical columns (two per object column) exceed NFK_MAX_REC_COLS.  Every record call below
+    // takes LOGICAL columns; heartbeat programs (nfk_op: record ops, NFK_GUARD_CELL_ID) and
+    // SetCreationRecord's cells speak the device's physical columns.
     int AddRecord(const std::string& name, int rows, const std::vector<TDATA_TYPE>& cols);
     void SetRecordFlags(const std::string& cls, const std::string& rec, bool pub, bool priv, bool upload);
     // the device-side effect of a heartbeat name (see nfgpu.h op list): operands as device
@@ -400,6 +419,19 @@ public:
     // nothing and raises no event)
     bool SetRecordInt(const NFGUID& self, const std::string& strRecordName, int nRow, int nCol, int64_t nValue);
     bool SetRecordFloat(const NFGUID& self, const std::string& strRecordName, int nRow, int nCol, double dwValue);
+    // NFIKernelModule::SetRecordObject -> NFCRecord::SetObject (RC:367-421) on an object column, queued in
+    // call order with the other record calls (nfk_set_record_objects): false for an unknown object or
+    // record, an invalid cell, a column that holds no NFGUID, a row unused now, and for a value equal
+    // (both halves) to the cell's as the reference holds it now — read-your-writes, one
+    // nfk_get_record_objects.  Cost per call, not measured: a Flush, the (object, record)'s used-row mask
+    // (one device read per window, then cached) and a synchronous read of the cell's two words that
+    // waits for the world's stream — SetRecordInt pays only the cached mask, because it does not
+    // answer the equal-value case; code that sets many object cells per frame pays one stream wait each.
+    // SetRecordInt / SetRecordFloat on an object column return false (RC:189).
+    // GetRecordObject: NFCRecord::GetObject (RC:697-716), NULL_OBJECT for an unused row or another type.
+    // The new entry points are looked up at first use; a library without them: std::runtime_error.
+    bool SetRecordObject(const NFGUID& self, const std::string& strRecordName, int nRow, int nCol, const NFGUID& value);
+    NFGUID GetRecordObject(const NFGUID& self, const std::string& strRecordName, int nRow, int nCol);
     // Record rows (NFCRecord::AddRow / Remove / IsUsed, NFIKernelModule::ClearRecord; RC:111, 1086,
     // 1209, KM:492), queued in call order with the SetRecord calls; Add / Del / Cover record events
     // are delivered with the frame.  AddRow returns the row it takes (-1 = the first unused row; no
@@ -431,6 +463,14 @@ public:
     int FindRowByColValue(const NFGUID& self, const std::string& strRecordName, int nCol, const std::vector<TData>& var,
                           std::vector<int>& varResult);
     bool QueryRow(const NFGUID& self, const std::string& strRecordName, int nRow, std::vector<TData>& varList);
+    // NFCRecord::FindObject (RC:957-987): rows whose used cell equals the NFGUID in both halves
+    // (NULL_OBJECT finds the used rows that hold it), one nfk_find_objects; FindRowByColValue with a
+    // TDATA_OBJECT var element 0 comes here with var's element nCol (NULL_OBJECT past its end or for
+    // another type, RC:806); QueryRow returns an object cell as one TDATA_OBJECT; FindRows takes
+    // TDATA_OBJECT finds (a batch's object finds go in one nfk_find_objects call beside the
+    // nfk_find_rows call of the others)
+    int FindObject(const NFGUID& self, const std::string& strRecordName, int nCol, const NFGUID& value,
+                   std::vector<int>& varResult);
     // a frame-level batch of finds in one nfk_find_rows call: one (object, record, column, value)
     // per entry, value.GetType() the find's type; hits[i].mask bit r: row r is a hit;
     // hits[i].invalid where the single call would return -1 (its mask is then 0)

@@ -44,6 +44,17 @@ extern "C" {
 #define NFK_MAX_REC_COLS 16
 #define NFK_MAX_TOUCH 12
 
+/* record column types (nfk_define_record).  An object (NFGUID) column is TWO adjacent physical
+ * columns: its data half (nData64) at column c and its head half (nHead64) at column c + 1, "data,
+ * then head" as an entity row stores an object property.  A cell of it is named by the column of its
+ * data half.  Whatever moves whole rows or column vectors carries an object cell as its two words:
+ * nfk_load_record / nfk_read_record, the AddRow values of nfk_record_rows, export / import rows
+ * (nfk_row_words), nfk_snapshot_objects' cells, and nfk_get_records (a half is a word). */
+#define NFK_REC_INT 0
+#define NFK_REC_F64 1
+#define NFK_REC_OBJ_DATA 2 /* an NFGUID's data half; the next column must be NFK_REC_OBJ_HEAD */
+#define NFK_REC_OBJ_HEAD 3 /* its head half; the column before must be NFK_REC_OBJ_DATA */
+
 /* property / record visibility flags, NFIProperty::GetPublic/GetPrivate/GetUpload */
 #define NFK_PUBLIC 1
 #define NFK_PRIVATE 2
@@ -200,6 +211,10 @@ typedef struct nfk_outputs {
      * half (nData64), these its head half (nHead64); other events leave them unwritten.  NULL in a
      * world without object properties. */
     const uint64_t* ev_old_h; const uint64_t* ev_new_h;
+    /* Update events of object record cells (rrc op 0 on an NFK_REC_OBJ_DATA column; one event per
+     * cell, never one on the head column): re_old / re_new hold the data halves, these the head
+     * halves; other record events leave them unwritten.  NULL in a world without object record columns. */
+    const uint64_t* re_old_h; const uint64_t* re_new_h;
 } nfk_outputs;
 
 /* ---- lifetime: NFCKernelModule ctor/Init/AfterInit (KM:17,51,1490) ---- */
@@ -212,7 +227,10 @@ const char* nfk_last_error(void);
 int nfk_set_prop_flags(void* world, int32_t cls, const uint8_t* flags /* [n_int+n_flt+n_obj]: the object
                                                                          properties' flags behind the others */);
 int nfk_define_record(void* world, int32_t rec, int32_t rows, int32_t cols,
-                      const uint8_t* col_types /* [cols] 0=int64 1=f64 */,
+                      const uint8_t* col_types /* [cols] NFK_REC_*: 0=int64 1=f64, 2 then 3 = an NFGUID's
+                                                   data and head halves (cols counts both; a 2 without
+                                                   a 3 behind it or a 3 without a 2 before it:
+                                                   NFK_ERR_ARG) */,
                       const uint8_t* flags_per_class /* [n_class] */);
 /* heartbeat kind program; replaces the functor passed to AddSchedule (SM:218) */
 int nfk_define_kind(void* world, int32_t kind, const nfk_op* ops, int32_t n_ops);
@@ -305,6 +323,18 @@ int nfk_get_objects(void* world, int32_t n, const int64_t* guid_head, const int6
  * RC:250).  NFK_ERR_NOTFOUND for an unknown GUID, NFK_ERR_ARG for a cell outside the record. */
 int nfk_set_records(void* world, int32_t n, const int64_t* guid_head, const int64_t* guid_data, const int32_t* rec,
                     const int32_t* row, const int32_t* col, const uint8_t* is_float, const uint64_t* bits);
+/* NFIKernelModule::SetRecordObject -> NFCRecord::SetObject (RC:367-421): queued in call order WITH the
+ * window's nfk_set_records / nfk_record_rows calls on the same (object, record), applied at the start
+ * of the next frame; refused on a row unused at that point of the call order; a value whose two halves
+ * both equal the cell's changes nothing and logs nothing, otherwise both halves are written together.
+ * col names the data half (NFK_REC_OBJ_DATA), else NFK_ERR_ARG; the other errors as nfk_set_records.
+ * nfk_set_records on either half of an object column writes nothing (a call of another type than
+ * its column, RC:189), with or without is_float: no call writes one half alone.  A cell that ends the
+ * frame different from its frame-start value in either half raises ONE Update event at the data
+ * half's column (re_old / re_new the data halves, re_old_h / re_new_h the head halves). */
+int nfk_set_record_objects(void* world, int32_t n, const int64_t* guid_head, const int64_t* guid_data,
+                           const int32_t* rec, const int32_t* row, const int32_t* col, const int64_t* val_head,
+                           const int64_t* val_data);
 
 /* ---- record row operations, queued in call order with the SetRecord calls:
  *   op 1  NFCRecord::AddRow(row, values) (RC:111-180): row -1 = the first unused row (none: nothing
@@ -334,6 +364,11 @@ int nfk_get_used_rows(void* world, int32_t n, const int64_t* guid_head, const in
  * row the record does not use.  NFK_ERR_NOTFOUND / NFK_ERR_ARG as nfk_set_records. */
 int nfk_get_records(void* world, int32_t n, const int64_t* guid_head, const int64_t* guid_data, const int32_t* rec,
                     const int32_t* row, const int32_t* col, uint64_t* bits);
+/* NFCRecord::GetObject (RC:697-716) of object cells (col: the data half's column, else NFK_ERR_ARG):
+ * read-your-writes as nfk_get_records; (0, 0), NULL_OBJECT, for a row the record does not use */
+int nfk_get_record_objects(void* world, int32_t n, const int64_t* guid_head, const int64_t* guid_data,
+                           const int32_t* rec, const int32_t* row, const int32_t* col, int64_t* val_head,
+                           int64_t* val_data);
 
 /* ---- property reads: NFIKernelModule::GetPropertyInt/Float (KM:401-425) ----
  * The value the reference would return now: the world's value after the last frame (waits for
@@ -416,6 +451,8 @@ int nfk_read_events(void* world, int32_t* ev_obj, int32_t* ev_pid, uint64_t* ev_
 /* the head halves of the object-property events, dense like nfk_read_events (0 for other events) */
 int nfk_read_events_obj(void* world, uint64_t* ev_old_h, uint64_t* ev_new_h);
 int nfk_read_rec_events(void* world, int32_t* re_obj, uint32_t* re_rrc, uint64_t* re_old, uint64_t* re_new);
+/* the head halves of the object-cell Update events, dense like nfk_read_rec_events (0 for other events) */
+int nfk_read_rec_events_obj(void* world, uint64_t* re_old_h, uint64_t* re_new_h);
 int nfk_read_fired(void* world, int32_t* fi_obj, int32_t* fi_kind, int32_t* fi_remain);
 /* dense CSR over [prop events ++ record events]: msg_off[n_ev + n_re + 1], recipients as objects */
 int nfk_read_fanout(void* world, uint32_t* msg_off, int32_t* msg_rcpt_obj);
@@ -434,6 +471,8 @@ int nfk_read_fanout(void* world, uint32_t* msg_off, int32_t* msg_rcpt_obj);
 #define NFK_READ_FIRED_GUID_ORDER 2u /* with NFK_READ_FIRED: (NFGUID, kind) order; else frame order */
 #define NFK_READ_EVENTS 4u           /* property and record events */
 #define NFK_READ_FANOUT 8u           /* with NFK_READ_EVENTS: the recipient CSR */
+/* nfk_read_frame clears and fills sizeof(nfk_frame_host) bytes, and the struct may grow at its end
+ * (re_old_h / re_new_h did): a caller is built against the header of the library it loads. */
 typedef struct nfk_frame_host {
     int64_t n_ev, n_re, n_fi, n_msgs;
     const int32_t* ev_obj; const int32_t* ev_pid; const uint64_t* ev_old; const uint64_t* ev_new;
@@ -443,6 +482,9 @@ typedef struct nfk_frame_host {
     const uint32_t* msg_off;   /* [n_ev + n_re + 1] */
     const int32_t* msg_rcpt;   /* [n_msgs] object indices */
     int64_t bytes;             /* bytes copied to the host */
+    /* head halves of the object record cells' Update events (re_old / re_new: the data halves), 0
+     * for the other record events; NULL in a world without object record columns */
+    const uint64_t* re_old_h; const uint64_t* re_new_h;
 } nfk_frame_host;
 int nfk_read_frame(void* world, uint32_t what, nfk_frame_host* out);
 
@@ -539,9 +581,19 @@ int nfk_find_rows(void* world, int32_t n, const int64_t* guid_head, const int64_
                   const int32_t* col, const uint64_t* bits, uint64_t* masks);
 int nfk_find_rows_obj(void* world, int32_t n, const int32_t* obj, const int32_t* rec, const int32_t* col,
                       const uint64_t* bits, uint64_t* masks);
-/* the last nfk_find_rows / nfk_find_rows_obj of the world: its launch's device time in ms (0 unless
- * nfk_set_profiling is on), the bytes read back and the finds answered on the host (each pointer
- * may be null) */
+/* NFCRecord::FindObject (RC:957-987): bit r of masks[i] is set when row r is used and BOTH halves of
+ * its cell in the object column col[i] (the data half's column, else NFK_ERR_ARG) equal the argument.
+ * A find of NULL_OBJECT (0, 0) finds the used rows that hold it, as the reference does.  One launch
+ * (k_find_objects: nfk_find_rows' shape, the head word read rows words behind the data word); the
+ * read-your-writes rule, the import buffer, the errors and nfk_find_stats are nfk_find_rows'.
+ * nfk_find_rows on either half of an object column is NFK_ERR_ARG. */
+int nfk_find_objects(void* world, int32_t n, const int64_t* guid_head, const int64_t* guid_data, const int32_t* rec,
+                     const int32_t* col, const int64_t* val_head, const int64_t* val_data, uint64_t* masks);
+int nfk_find_objects_obj(void* world, int32_t n, const int32_t* obj, const int32_t* rec, const int32_t* col,
+                         const int64_t* val_head, const int64_t* val_data, uint64_t* masks);
+/* the last nfk_find_rows / nfk_find_objects (or their _obj forms) of the world: its launch's device
+ * time in ms (0 unless nfk_set_profiling is on), the bytes read back and the finds answered on the
+ * host (each pointer may be null) */
 int nfk_find_stats(void* world, double* kernel_ms, int64_t* bytes, int32_t* n_host);
 
 /* ---- enter snapshots: the payloads of NFCGameServerNet_ServerModule::OnPropertyEnter (:271-393) and

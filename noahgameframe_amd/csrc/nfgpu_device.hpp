@@ -191,7 +191,7 @@ struct Tables {
     int32_t n_recops;
     int32_t rec_rows[NFK_MAX_RECORDS], rec_cols[NFK_MAX_RECORDS];
     uint32_t kind_has_recop;  // bit k: kind k has record ops
-    uint8_t rec_ctype[NFK_MAX_RECORDS][NFK_MAX_REC_COLS];  // 0 = int64, 1 = f64
+    uint8_t rec_ctype[NFK_MAX_RECORDS][NFK_MAX_REC_COLS];  // NFK_REC_*: int64, f64, an NFGUID's data / head half
 };
 
 // Everything a kernel needs, passed by value.

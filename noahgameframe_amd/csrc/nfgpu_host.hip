@@ -135,7 +135,7 @@ struct World {
     std::vector<std::vector<uint64_t>> init_props;
     std::vector<std::vector<uint64_t>> init_rcells, init_rused;
     std::vector<bool> rec_defined;
-    uint8_t rec_ctype[NFK_MAX_RECORDS][NFK_MAX_REC_COLS] = {};  // 0 = int64, 1 = f64
+    uint8_t rec_ctype[NFK_MAX_RECORDS][NFK_MAX_REC_COLS] = {};  // NFK_REC_*
 
     Tables tab{};
     bool kind_defined[NFK_MAX_KINDS] = {};
@@ -229,6 +229,16 @@ struct World {
     // 2 Remove, 3 ClearRecord
     struct RSOp { uint32_t obj, rrc; uint64_t bits; uint32_t op, aux; };
     std::vector<RSOp> rsq;
+    // the NFGUID head halves of the queued SetRecordObject calls (bits: the data halves), parallel
+    // to rsq and filled up lazily: shorter than rsq until the window's first such call (rsq_head)
+    std::vector<uint64_t> rsq_h;
+    uint64_t rsq_head(size_t k) const { return k < rsq_h.size() ? rsq_h[k] : 0ull; }
+    bool rec_obj = false;  // a record has an object column (fixed at nfk_commit)
+    // the head halves of the object cells' Update events, tile-staged beside Dev::re_old / re_new
+    // (rec_obj), and the frame's RecHeads (the SetRecord kernels' second argument)
+    uint64_t* re_old_h = nullptr;
+    uint64_t* re_new_h = nullptr;
+    RecHeads rheads{};
     std::vector<uint64_t> rvals;  // AddRow values, NFK_MAX_REC_COLS words each
     std::unordered_map<uint64_t, std::vector<uint32_t>> rq_index;  // (object << 3 | record) -> its queued calls
     std::unordered_map<uint64_t, uint64_t> ucache;  // (object << 3 | record) -> used mask read this window
@@ -394,6 +404,7 @@ int drop_window(World* w, int r) {
     w->sa_pids[0] = w->sa_pids[1] = 0;
     w->hops.clear();
     w->rsq.clear();
+    w->rsq_h.clear();
     w->rvals.clear();
     w->rq_index.clear();
     w->ucache.clear();
@@ -977,7 +988,8 @@ int grow_rec_tiles(World* w, int64_t per_tile) {
     int r;
     if ((r = regrow(w, (void**)&d.re_rrc, n * 4)) ||
         (r = regrow(w, (void**)&d.re_old, n * 8)) || (r = regrow(w, (void**)&d.re_new, n * 8)) ||
-        (r = regrow(w, (void**)&d.re_moff, n * 4))) {
+        (r = regrow(w, (void**)&d.re_moff, n * 4)) ||
+        (w->rec_obj && ((r = regrow(w, (void**)&w->re_old_h, n * 8)) || (r = regrow(w, (void**)&w->re_new_h, n * 8))))) {
         d.re_tcap = 0;
         return r;
     }
@@ -1933,13 +1945,21 @@ int nfk_define_record(void* world, int32_t rec, int32_t rows, int32_t cols, cons
         cols > NFK_MAX_REC_COLS || !flags_per_class)
         return fail(NFK_ERR_ARG, "bad record definition");
     if (w->committed) return fail(NFK_ERR_STATE, "schema is fixed after commit");
+    // an object column is a data half with its head half right behind it (checked before anything
+    // is changed)
+    for (int c = 0; col_types && c < cols; c++) {
+        const int t = col_types[c];
+        if (t > NFK_REC_OBJ_HEAD)
+            return fail(NFK_ERR_ARG, "record column type must be 0 (int64), 1 (f64) or 2, 3 (an NFGUID's halves)");
+        if (t == NFK_REC_OBJ_DATA && (c + 1 >= cols || col_types[c + 1] != NFK_REC_OBJ_HEAD))
+            return fail(NFK_ERR_ARG, "record column " + std::to_string(c) + ": a data half (2) without its head half (3) behind it");
+        if (t == NFK_REC_OBJ_HEAD && (c == 0 || col_types[c - 1] != NFK_REC_OBJ_DATA))
+            return fail(NFK_ERR_ARG, "record column " + std::to_string(c) + ": a head half (3) without its data half (2) before it");
+    }
     w->tab.rec_rows[rec] = rows;
     w->tab.rec_cols[rec] = cols;
     for (int c = 0; c < w->cfg.n_class; c++) w->tab.rflags[c][rec] = flags_per_class[c];
-    for (int c = 0; c < cols; c++) {
-        if (col_types && col_types[c] > 1) return fail(NFK_ERR_ARG, "record column type must be 0 (int64) or 1 (f64)");
-        w->rec_ctype[rec][c] = col_types ? col_types[c] : 0;
-    }
+    for (int c = 0; c < NFK_MAX_REC_COLS; c++) w->rec_ctype[rec][c] = col_types && c < cols ? col_types[c] : 0;
     w->rec_defined[rec] = true;
     return NFK_OK;
 }
@@ -1954,7 +1974,8 @@ static int check_guard_cell(World* w, const nfk_op& op) {
         return fail(NFK_ERR_ARG, "NFK_GUARD_CELL: row " + std::to_string(row) + " outside record " + std::to_string(r) + "'s rows");
     if (col >= w->tab.rec_cols[r])
         return fail(NFK_ERR_ARG, "NFK_GUARD_CELL: column " + std::to_string(col) + " outside record " + std::to_string(r) + "'s columns");
-    if (w->rec_ctype[r][col] != 0) return fail(NFK_ERR_ARG, "NFK_GUARD_CELL: the guard's column is not an int column");
+    if (w->rec_ctype[r][col] != NFK_REC_INT)  // (f64, or a half of an object column)
+        return fail(NFK_ERR_ARG, "NFK_GUARD_CELL: the guard's column is not an int column");
     return NFK_OK;
 }
 
@@ -2012,7 +2033,8 @@ int nfk_define_kind(void* world, int32_t kind, const nfk_op* ops, int32_t n_ops)
                 return fail(NFK_ERR_ARG, "record op on undefined record/col");
             // NFCRecord::SetInt / SetFloat refuse a cell of the other type (RC:189, RC:250): such
             // an op could never change a cell, so it is rejected with the kind
-            if (w->rec_ctype[r][col] != (op.code == NFK_OP_RFAFFINE ? 1 : 0))
+            // (a half of an object column is neither)
+            if (w->rec_ctype[r][col] != (op.code == NFK_OP_RFAFFINE ? NFK_REC_F64 : NFK_REC_INT))
                 return fail(NFK_ERR_ARG, "record op type does not match the column type");
             break;
         }
@@ -2170,6 +2192,9 @@ int nfk_commit(void* world) {
     for (int r = 0; r < NR; r++) any_rec = any_rec || w->rec_defined[r];
     d.has_recops = nro > 0 || any_rec;
     memcpy(w->tab.rec_ctype, w->rec_ctype, sizeof(w->tab.rec_ctype));
+    w->rec_obj = false;
+    for (int r = 0; r < NR; r++)
+        for (int c = 0; w->rec_defined[r] && c < w->tab.rec_cols[r]; c++) w->rec_obj = w->rec_obj || w->rec_ctype[r][c] == NFK_REC_OBJ_DATA;
     ALLOC(w->tab_d, sizeof(Tables));
     ALLOC(d.tally, (size_t)3 * kTallyN * 8 * 8);
     ALLOC(w->ctrl, sizeof(Ctrl));
@@ -2245,6 +2270,10 @@ int nfk_commit(void* world) {
     ALLOC(d.re_old, re_n * 8);
     ALLOC(d.re_new, re_n * 8);
     ALLOC(d.re_moff, re_n * 4);
+    if (w->rec_obj) {
+        ALLOC(w->re_old_h, re_n * 8);
+        ALLOC(w->re_new_h, re_n * 8);
+    }
     ALLOC(d.msg_rcpt, d.msg_cap * 4);
     d.tab = w->tab_d;
     d.ctrl = w->ctrl;
@@ -2464,10 +2493,41 @@ int nfk_set_records(void* world, int32_t n, const int64_t* gh, const int64_t* gd
     w->rsq.reserve(w->rsq.size() + n);
     for (int32_t i = 0; i < n; i++) {
         // NFCRecord::SetInt / SetFloat on a column of the other type write nothing (RC:189 / RC:250)
-        if (is_float && (is_float[i] != 0) != (w->rec_ctype[rec[i]][col[i]] != 0)) continue;
+        // a half of an object column takes neither (nothing writes one half of a pair alone)
+        const int ct = w->rec_ctype[rec[i]][col[i]];
+        if (ct >= NFK_REC_OBJ_DATA || (is_float && (is_float[i] != 0) != (ct == NFK_REC_F64))) continue;
         w->rq_index[((uint64_t)w->look[i] << 3) | (uint32_t)rec[i]].push_back((uint32_t)w->rsq.size());
         w->rsq.push_back(World::RSOp{(uint32_t)w->look[i], ((uint32_t)rec[i] << 16) | ((uint32_t)row[i] << 8) | (uint32_t)col[i],
                                      bits[i], 0u, 0u});
+    }
+    return NFK_OK;
+}
+
+int nfk_set_record_objects(void* world, int32_t n, const int64_t* gh, const int64_t* gd, const int32_t* rec,
+                           const int32_t* row, const int32_t* col, const int64_t* vh, const int64_t* vd) {
+    World* w = (World*)world;
+    if (!w || n < 0 || (n && (!gh || !gd || !rec || !row || !col || !vh || !vd))) return fail(NFK_ERR_ARG, "null argument");
+    if (!w->committed) return fail(NFK_ERR_STATE, "commit first");
+    w->look.resize(n);
+    if (int rl = find_many_par(w, n, gh, gd, w->look.data())) return rl;
+    for (int32_t i = 0; i < n; i++) {
+        if (w->look[i] < 0)  // "There is no object" (KM: SetRecordObject)
+            return fail(NFK_ERR_NOTFOUND, "no object " + std::to_string(gh[i]) + "-" + std::to_string(gd[i]));
+        const int32_t r = rec[i];
+        if (r < 0 || r >= w->cfg.n_rec || !w->rec_defined[r] || row[i] < 0 || row[i] >= w->tab.rec_rows[r] ||
+            col[i] < 0 || col[i] >= w->tab.rec_cols[r])
+            return fail(NFK_ERR_ARG, "record cell out of range");
+        if (w->rec_ctype[r][col[i]] != NFK_REC_OBJ_DATA)
+            return fail(NFK_ERR_ARG, "not the data half of an object column");
+    }
+    // one queue with the int / f64 Sets and the row operations: the call order on a record is kept
+    w->rsq.reserve(w->rsq.size() + n);
+    w->rsq_h.resize(w->rsq.size(), 0);
+    for (int32_t i = 0; i < n; i++) {
+        w->rq_index[((uint64_t)w->look[i] << 3) | (uint32_t)rec[i]].push_back((uint32_t)w->rsq.size());
+        w->rsq.push_back(World::RSOp{(uint32_t)w->look[i], ((uint32_t)rec[i] << 16) | ((uint32_t)row[i] << 8) | (uint32_t)col[i],
+                                     (uint64_t)vd[i], 0u, 0u});
+        w->rsq_h.push_back((uint64_t)vh[i]);
     }
     return NFK_OK;
 }
@@ -2603,17 +2663,27 @@ int nfk_get_used_rows(void* world, int32_t n, const int64_t* gh, const int64_t* 
 // used state at that call, AddRow / Remove / ClearRecord on the mask (RC:111, RC:1086, RC:1109).  A
 // Remove leaves the cell's value behind (RC:1086-1107); an AddRow without values writes 0.  A row's
 // result depends on no other row's cell.  Shared by nfk_get_records and nfk_find_rows.
-static void replay_column(const World* w, int32_t o, int32_t r, int32_t col, uint64_t& u, uint64_t* c) {
+// The pair form (ch != null, col the data half of an object column): c the data halves, ch the head
+// halves; SetRecordObject writes both (RC:367-421), AddRow both words of its values.  Without ch a
+// half column replays as the word it is (nfk_get_records): a queued SetRecordObject is named by its
+// data half's column and writes the head column's word too.
+static void replay_column(const World* w, int32_t o, int32_t r, int32_t col, uint64_t& u, uint64_t* c,
+                          uint64_t* ch = nullptr) {
     auto it = w->rq_index.find(((uint64_t)o << 3) | (uint32_t)r);
     if (it == w->rq_index.end()) return;
     const int32_t rows = w->tab.rec_rows[r];
+    const int ct = w->rec_ctype[r][col];
+    const int setc = ct == NFK_REC_OBJ_HEAD ? col - 1 : col;  // the column a Set of this cell names
     for (uint32_t k : it->second) {
         const World::RSOp& x = w->rsq[k];
         const int xr = (int)((x.rrc >> 8) & 0xFF), xc = (int)(x.rrc & 0xFF);
         if (x.op == 0) {
-            if (xc != col || !((u >> xr) & 1)) continue;
+            if (xc != setc || !((u >> xr) & 1)) continue;
             const uint64_t b = x.bits;
-            if (w->rec_ctype[r][col]) {
+            if (ct >= NFK_REC_OBJ_DATA) {
+                c[xr] = ct == NFK_REC_OBJ_HEAD ? w->rsq_head(k) : b;
+                if (ch) ch[xr] = w->rsq_head(k);
+            } else if (ct == NFK_REC_F64) {
                 double bd, cd;
                 memcpy(&bd, &b, 8);
                 memcpy(&cd, &c[xr], 8);
@@ -2631,6 +2701,7 @@ static void replay_column(const World* w, int32_t o, int32_t r, int32_t col, uin
             }
             u |= 1ull << rr;
             c[rr] = x.aux == 0xFFFFFFFFu ? 0ull : w->rvals[(size_t)x.aux * NFK_MAX_REC_COLS + col];
+            if (ch) ch[rr] = x.aux == 0xFFFFFFFFu ? 0ull : w->rvals[(size_t)x.aux * NFK_MAX_REC_COLS + col + 1];
         } else if (x.op == 2) {
             u &= ~(1ull << xr);
         } else {
@@ -2639,11 +2710,11 @@ static void replay_column(const World* w, int32_t o, int32_t r, int32_t col, uin
     }
 }
 
-int nfk_get_records(void* world, int32_t n, const int64_t* gh, const int64_t* gd, const int32_t* rec,
-                    const int32_t* row, const int32_t* col, uint64_t* bits) {
-    World* w = (World*)world;
-    if (!w || n < 0 || (n && (!gh || !gd || !rec || !row || !col || !bits))) return fail(NFK_ERR_ARG, "null argument");
-    if (!w->committed) return fail(NFK_ERR_STATE, "commit first");
+// nfk_get_records (heads null: the cells as the words they are) and nfk_get_record_objects (heads:
+// the cells' head halves, bits their data halves; col names the data half, checked before anything
+// is read): one lookup per query, the masks in one gather, both words of a pair in the second
+static int get_record_cells(World* w, int32_t n, const int64_t* gh, const int64_t* gd, const int32_t* rec,
+                            const int32_t* row, const int32_t* col, uint64_t* bits, uint64_t* heads) {
     std::vector<int32_t> obj(n);
     if (int rl = find_many_par(w, n, gh, gd, obj.data())) return rl;
     for (int32_t i = 0; i < n; i++) {
@@ -2652,11 +2723,13 @@ int nfk_get_records(void* world, int32_t n, const int64_t* gh, const int64_t* gd
         if (r < 0 || r >= w->cfg.n_rec || !w->rec_defined[r] || row[i] < 0 || row[i] >= w->tab.rec_rows[r] ||
             col[i] < 0 || col[i] >= w->tab.rec_cols[r])
             return fail(NFK_ERR_ARG, "record cell out of range");
+        if (heads && w->rec_ctype[r][col[i]] != NFK_REC_OBJ_DATA)
+            return fail(NFK_ERR_ARG, "not the data half of an object column");
     }
     // every query's used-row mask (this window's cache, else one gather), then the cells of the
     // rows the device holds as used in a second: a cell's place in its vector follows from the
     // mask (rec_pos); a row the device holds unused reads 0 unless a queued AddRow writes it
-    std::vector<uint64_t> um(n), cv(n, 0);
+    std::vector<uint64_t> um(n), cv(n, 0), hv(heads ? n : 0, 0);
     {
         std::vector<uint64_t> addr;
         std::vector<int32_t> miss;
@@ -2696,20 +2769,42 @@ int nfk_get_records(void* world, int32_t n, const int64_t* gh, const int64_t* gd
                 return fail(NFK_ERR_STATE, "object without a slot");
             }
             addr.push_back((uint64_t)(uintptr_t)cell);
+            if (heads) addr.push_back((uint64_t)(uintptr_t)(cell + rows));  // (the same place of the next column vector)
             at.push_back(i);
         }
         std::vector<uint64_t> got(addr.size());
         if (int r = read_abs(w, addr, got.data())) return r;
-        for (size_t q = 0; q < at.size(); q++) cv[at[q]] = got[q];
+        for (size_t q = 0; q < at.size(); q++) {
+            cv[at[q]] = got[heads ? 2 * q : q];
+            if (heads) hv[at[q]] = got[2 * q + 1];
+        }
     }
     for (int32_t i = 0; i < n; i++) {
-        uint64_t u = um[i], c[64] = {};
+        uint64_t u = um[i], c[64] = {}, ch[64] = {};
         c[row[i]] = cv[i];
-        replay_column(w, obj[i], rec[i], col[i], u, c);
-        // NFCRecord::GetInt / GetFloat of an unused row (RC:623): 0
+        if (heads) ch[row[i]] = hv[i];
+        replay_column(w, obj[i], rec[i], col[i], u, c, heads ? ch : nullptr);
+        // NFCRecord::GetInt / GetFloat / GetObject of an unused row (RC:623, RC:704): 0 / NULL_OBJECT
         bits[i] = ((u >> row[i]) & 1) ? c[row[i]] : 0;
+        if (heads) heads[i] = ((u >> row[i]) & 1) ? ch[row[i]] : 0;
     }
     return NFK_OK;
+}
+
+int nfk_get_records(void* world, int32_t n, const int64_t* gh, const int64_t* gd, const int32_t* rec,
+                    const int32_t* row, const int32_t* col, uint64_t* bits) {
+    World* w = (World*)world;
+    if (!w || n < 0 || (n && (!gh || !gd || !rec || !row || !col || !bits))) return fail(NFK_ERR_ARG, "null argument");
+    if (!w->committed) return fail(NFK_ERR_STATE, "commit first");
+    return get_record_cells(w, n, gh, gd, rec, row, col, bits, nullptr);
+}
+
+int nfk_get_record_objects(void* world, int32_t n, const int64_t* gh, const int64_t* gd, const int32_t* rec,
+                           const int32_t* row, const int32_t* col, int64_t* vh, int64_t* vd) {
+    World* w = (World*)world;
+    if (!w || n < 0 || (n && (!gh || !gd || !rec || !row || !col || !vh || !vd))) return fail(NFK_ERR_ARG, "null argument");
+    if (!w->committed) return fail(NFK_ERR_STATE, "commit first");
+    return get_record_cells(w, n, gh, gd, rec, row, col, (uint64_t*)vd, (uint64_t*)vh);
 }
 
 // ---- record finds (nfk_find_rows): NFCRecord::FindInt / FindFloat (RC:830-899) ----
@@ -2731,9 +2826,11 @@ static int rec_addrs(World* w, int32_t o, int32_t r, const uint64_t** cells, con
     return NFK_OK;
 }
 
-// the finds of resolved objects (obj[i] < 0: unknown; gh / gd for the message, or null)
+// the finds of resolved objects (obj[i] < 0: unknown; gh / gd for the message, or null); heads: the
+// arguments' NFGUID head halves (bits: the data halves) of a FindObject batch (k_find_objects), null
+// for FindInt / FindFloat (k_find_rows)
 static int find_rows(World* w, int32_t n, const int32_t* obj, const int64_t* gh, const int64_t* gd, const int32_t* rec,
-                     const int32_t* col, const uint64_t* bits, uint64_t* masks) {
+                     const int32_t* col, const uint64_t* bits, uint64_t* masks, const uint64_t* heads = nullptr) {
     w->f_kernel_ms = 0;
     w->f_bytes = 0;
     w->f_host = 0;
@@ -2745,6 +2842,10 @@ static int find_rows(World* w, int32_t n, const int32_t* obj, const int64_t* gh,
         const int32_t r = rec[i];
         if (r < 0 || r >= w->cfg.n_rec || !w->rec_defined[r]) return fail(NFK_ERR_ARG, "bad record");
         if (col[i] < 0 || col[i] >= w->tab.rec_cols[r]) return fail(NFK_ERR_ARG, "record column out of range");
+        const int ct = w->rec_ctype[r][col[i]];
+        if (heads ? ct != NFK_REC_OBJ_DATA : ct >= NFK_REC_OBJ_DATA)
+            return fail(NFK_ERR_ARG, heads ? "not the data half of an object column"
+                                           : "a half of an object column (nfk_find_objects finds NFGUIDs)");
         max_rows = std::max(max_rows, (int)w->tab.rec_rows[r]);
     }
     if (n == 0) return NFK_OK;
@@ -2753,7 +2854,8 @@ static int find_rows(World* w, int32_t n, const int32_t* obj, const int64_t* gh,
 
     // descriptors in pinned memory, the masks behind them; a query whose record has queued calls
     // in this window is left out of the batch (host: below)
-    const size_t o_m = align16((size_t)n * sizeof(FindDev)), tot = o_m + (size_t)n * 8;
+    const size_t dsz = heads ? sizeof(FindObjDev) : sizeof(FindDev);
+    const size_t o_m = align16((size_t)n * dsz), tot = o_m + (size_t)n * 8;
     if (int r = dev_reserve(w, &w->f_dev, &w->f_dcap, tot)) return r;
     if (tot > w->f_pcap) {
         if (w->f_pin) HIPCHK(hipHostFree(w->f_pin));
@@ -2764,6 +2866,7 @@ static int find_rows(World* w, int32_t n, const int32_t* obj, const int64_t* gh,
         w->f_pcap = c;
     }
     FindDev* hq = (FindDev*)w->f_pin;
+    FindObjDev* hqo = (FindObjDev*)w->f_pin;
     const uint64_t* hm = (const uint64_t*)(w->f_pin + o_m);
     std::vector<int32_t> host;  // queries answered on the host
     const bool queued = !w->rq_index.empty();
@@ -2776,11 +2879,22 @@ static int find_rows(World* w, int32_t n, const int32_t* obj, const int64_t* gh,
         }
         const uint64_t *cells, *used;
         if (int e = rec_addrs(w, o, r, &cells, &used)) return e;
+        if (heads) {
+            FindObjDev f;
+            f.used = (uint64_t)(uintptr_t)used;
+            f.colv = (uint64_t)(uintptr_t)(cells + (size_t)col[i] * w->tab.rec_rows[r]);
+            f.arg_d = bits[i];
+            f.arg_h = heads[i];
+            f.rows = w->tab.rec_rows[r];
+            f.pad = 0;
+            hqo[nd++] = f;
+            continue;
+        }
         FindDev f;
         f.used = (uint64_t)(uintptr_t)used;
         f.colv = (uint64_t)(uintptr_t)(cells + (size_t)col[i] * w->tab.rec_rows[r]);
         f.rows = w->tab.rec_rows[r];
-        f.flt = w->rec_ctype[r][col[i]] ? 1 : 0;
+        f.flt = w->rec_ctype[r][col[i]] == NFK_REC_F64 ? 1 : 0;
         f.arg = bits[i];
         hq[nd++] = f;
     }
@@ -2790,11 +2904,15 @@ static int find_rows(World* w, int32_t n, const int32_t* obj, const int64_t* gh,
         if (timed)
             for (auto& e : w->f_ev)
                 if (!e) HIPCHK(hipEventCreate(&e));
-        HIPCHK(hipMemcpyAsync(D, hq, (size_t)nd * sizeof(FindDev), hipMemcpyHostToDevice, w->stream));
+        HIPCHK(hipMemcpyAsync(D, w->f_pin, (size_t)nd * dsz, hipMemcpyHostToDevice, w->stream));
         if (timed) HIPCHK(hipEventRecord(w->f_ev[0], w->stream));
         const int64_t threads = (int64_t)nd << lg;
-        hipLaunchKernelGGL(k_find_rows, dim3((unsigned)((threads + kTPB - 1) / kTPB)), dim3(kTPB), 0, w->stream,
-                           (const FindDev*)D, nd, lg, (uint64_t*)(D + o_m));
+        if (heads)
+            hipLaunchKernelGGL(k_find_objects, dim3((unsigned)((threads + kTPB - 1) / kTPB)), dim3(kTPB), 0, w->stream,
+                               (const FindObjDev*)D, nd, lg, (uint64_t*)(D + o_m));
+        else
+            hipLaunchKernelGGL(k_find_rows, dim3((unsigned)((threads + kTPB - 1) / kTPB)), dim3(kTPB), 0, w->stream,
+                               (const FindDev*)D, nd, lg, (uint64_t*)(D + o_m));
         HIPCHK(hipGetLastError());
         if (timed) HIPCHK(hipEventRecord(w->f_ev[1], w->stream));
         HIPCHK(hipMemcpyAsync(w->f_pin + o_m, D + o_m, (size_t)nd * 8, hipMemcpyDeviceToHost, w->stream));
@@ -2833,8 +2951,12 @@ static int find_rows(World* w, int32_t n, const int32_t* obj, const int64_t* gh,
     if (int e = read_abs(w, addr, um.data())) return e;
     addr.clear();
     for (size_t j = 0; j < host.size(); j++) {
-        um[j] &= rec_rowm(w->tab.rec_rows[rec[host[j]]]);
-        for (int p = 0, np = __builtin_popcountll(um[j]); p < np; p++) addr.push_back((uint64_t)(uintptr_t)(colv[j] + p));
+        const int rows = w->tab.rec_rows[rec[host[j]]];
+        um[j] &= rec_rowm(rows);
+        const int np = __builtin_popcountll(um[j]);
+        for (int p = 0; p < np; p++) addr.push_back((uint64_t)(uintptr_t)(colv[j] + p));
+        // (an object find: the head halves, the same places of the next column vector)
+        for (int p = 0; heads && p < np; p++) addr.push_back((uint64_t)(uintptr_t)(colv[j] + rows + p));
     }
     std::vector<uint64_t> cv(addr.size());
     if (int e = read_abs(w, addr, cv.data())) return e;
@@ -2844,6 +2966,17 @@ static int find_rows(World* w, int32_t n, const int32_t* obj, const int64_t* gh,
         uint64_t u = um[j], c[64] = {};
         for (int row = 0; row < rows; row++)
             if ((u >> row) & 1) c[row] = cv[at++];  // (the used rows first, in row order: rec_pos)
+        if (heads) {  // NFCRecord::FindObject (RC:957-987): both halves, on the used rows
+            uint64_t ch[64] = {};
+            for (int row = 0; row < rows; row++)
+                if ((u >> row) & 1) ch[row] = cv[at++];
+            replay_column(w, obj[i], r, col[i], u, c, ch);
+            uint64_t m = 0;
+            for (int row = 0; row < rows; row++)
+                m |= (uint64_t)(((u >> row) & 1) && c[row] == bits[i] && ch[row] == heads[i]) << row;
+            masks[i] = m;
+            continue;
+        }
         replay_column(w, obj[i], r, col[i], u, c);
         uint64_t m = 0;
         double a;
@@ -2851,7 +2984,7 @@ static int find_rows(World* w, int32_t n, const int32_t* obj, const int64_t* gh,
         for (int row = 0; row < rows; row++) {
             if (!((u >> row) & 1)) continue;
             bool hit = c[row] == bits[i];
-            if (w->rec_ctype[r][col[i]]) {
+            if (w->rec_ctype[r][col[i]] == NFK_REC_F64) {
                 double v;
                 memcpy(&v, &c[row], 8);
                 hit = v == a;
@@ -2879,6 +3012,25 @@ int nfk_find_rows_obj(void* world, int32_t n, const int32_t* obj, const int32_t*
     if (!w || n < 0 || (n && (!obj || !rec || !col || !bits || !masks))) return fail(NFK_ERR_ARG, "null argument");
     if (!w->committed) return fail(NFK_ERR_STATE, "commit first");
     return find_rows(w, n, live_objects(w, n, obj), nullptr, nullptr, rec, col, bits, masks);
+}
+
+int nfk_find_objects(void* world, int32_t n, const int64_t* gh, const int64_t* gd, const int32_t* rec, const int32_t* col,
+                     const int64_t* vh, const int64_t* vd, uint64_t* masks) {
+    World* w = (World*)world;
+    if (!w || n < 0 || (n && (!gh || !gd || !rec || !col || !vh || !vd || !masks))) return fail(NFK_ERR_ARG, "null argument");
+    if (!w->committed) return fail(NFK_ERR_STATE, "commit first");
+    std::vector<int32_t> obj(n);
+    if (int rl = find_many_par(w, n, gh, gd, obj.data())) return rl;
+    return find_rows(w, n, obj.data(), gh, gd, rec, col, (const uint64_t*)vd, masks, (const uint64_t*)vh);
+}
+
+int nfk_find_objects_obj(void* world, int32_t n, const int32_t* obj, const int32_t* rec, const int32_t* col,
+                         const int64_t* vh, const int64_t* vd, uint64_t* masks) {
+    World* w = (World*)world;
+    if (!w || n < 0 || (n && (!obj || !rec || !col || !vh || !vd || !masks))) return fail(NFK_ERR_ARG, "null argument");
+    if (!w->committed) return fail(NFK_ERR_STATE, "commit first");
+    return find_rows(w, n, live_objects(w, n, obj), nullptr, nullptr, rec, col, (const uint64_t*)vd, masks,
+                     (const uint64_t*)vh);
 }
 
 int nfk_find_stats(void* world, double* kernel_ms, int64_t* bytes, int32_t* n_host) {
@@ -3957,7 +4109,7 @@ static int execute_frame(World* w, int64_t now_ms, bool calls_only) {
     rss_slot.clear();
     rss_g0.clear();
     std::vector<uint32_t> rss_l0, rl_slot, rl_rec, rl_c0, rl_ev0, rc_code, rc_aux;
-    std::vector<uint64_t> rc_bits;
+    std::vector<uint64_t> rc_bits, rc_bits_h;
     std::vector<uint64_t>& rowpairs = w->rowpairs;
     rowpairs.clear();
     std::vector<uint64_t>& rpk = w->rpk;
@@ -4021,6 +4173,7 @@ static int execute_frame(World* w, int64_t now_ms, bool calls_only) {
             rc_code.assign(rl_c0[npair], 0);
             rc_aux.assign(rl_c0[npair], 0);
             rc_bits.assign(rl_c0[npair], 0);
+            if (w->rec_obj) rc_bits_h.assign(rl_c0[npair], 0);
             rl_ev0.assign(npair, 0);
             std::vector<uint32_t> fill(rl_c0.begin(), rl_c0.end() - 1), evb(npair, 0);
             for (size_t i = 0; i < n_rq; i++) {
@@ -4031,6 +4184,7 @@ static int execute_frame(World* w, int64_t now_ms, bool calls_only) {
                 const uint32_t rec = x.rrc >> 16, row = (x.rrc >> 8) & 0xFF, col = x.rrc & 0xFF;
                 rc_code[at] = x.op | (row << 8) | (col << 16);
                 rc_bits[at] = x.bits;
+                if (w->rec_obj) rc_bits_h[at] = w->rsq_head(i);
                 if (x.op == 0) {  // its cell's group (binary search over the sorted groups)
                     const uint64_t key = ((uint64_t)(rowpairs[q] >> 3) << 19) | (x.rrc & 0x7FFFF);
                     size_t lo = 0, hi = rs_slot.size();
@@ -4137,7 +4291,10 @@ static int execute_frame(World* w, int64_t now_ms, bool calls_only) {
     size_t off_le = align16(off_lc + (nrl ? (nrl + 1) * 4 : 0)), off_cc = align16(off_le + nrl * 4);
     size_t off_ca = align16(off_cc + nrcall * 4), off_cb = align16(off_ca + nrcall * 4);
     size_t off_rv = align16(off_cb + nrcall * 8);
-    size_t total = align16(off_rv + (nrl ? nval * 8 : 0));
+    // the SetRecordObject calls' head halves, beside rs_bits and rc_bits (a world with an object column)
+    const bool robj = w->rec_obj;
+    size_t off_rbh = align16(off_rv + (nrl ? nval * 8 : 0)), off_cbh = align16(off_rbh + (robj ? nrc * 8 : 0));
+    size_t total = align16(off_cbh + (robj ? nrcall * 8 : 0));
     // device fold scratch: keys, sorted keys, call indices, sorted indices, group starts [ng + 1],
     // the groups (slot, property, first call [ng + 1]), the sorted values (and head halves), then
     // the radix sort's temporary storage
@@ -4190,7 +4347,7 @@ static int execute_frame(World* w, int64_t now_ms, bool calls_only) {
         }
     }
     if (nrss) {
-        int r = dev_reserve(w, (void**)&w->rs_buf, &w->rs_cap, std::max<size_t>(ngr, 1) * 16);
+        int r = dev_reserve(w, (void**)&w->rs_buf, &w->rs_cap, std::max<size_t>(ngr, 1) * (robj ? 32 : 16));
         if (r) return drop_window(w, r);
         r = dev_reserve(w, (void**)&w->rss_buf, &w->rss_cap, nrss * 16);
         if (r) return drop_window(w, r);
@@ -4213,6 +4370,10 @@ static int execute_frame(World* w, int64_t now_ms, bool calls_only) {
             memcpy(P + off_rf, rs_first.data(), (ngr + 1) * 4);
             uint64_t* rb = (uint64_t*)(P + off_rb);
             for (size_t i = 0; i < nrc; i++) rb[i] = w->rsq[rpk[i] & rim].bits;
+            if (robj) {
+                uint64_t* rbh = (uint64_t*)(P + off_rbh);
+                for (size_t i = 0; i < nrc; i++) rbh[i] = w->rsq_head(rpk[i] & rim);
+            }
             memcpy(P + off_ss, rss_slot.data(), nrss * 4);
             memcpy(P + off_sg, rss_g0.data(), nrss * 4);
         }
@@ -4225,6 +4386,7 @@ static int execute_frame(World* w, int64_t now_ms, bool calls_only) {
             memcpy(P + off_cc, rc_code.data(), nrcall * 4);
             memcpy(P + off_ca, rc_aux.data(), nrcall * 4);
             memcpy(P + off_cb, rc_bits.data(), nrcall * 8);
+            if (robj) memcpy(P + off_cbh, rc_bits_h.data(), nrcall * 8);
             if (nval) memcpy(P + off_rv, w->rvals.data(), nval * 8);
         }
         HIPCHK(hipMemcpyAsync(w->stage, w->pin, total, hipMemcpyHostToDevice, w->stream));
@@ -4257,6 +4419,13 @@ static int execute_frame(World* w, int64_t now_ms, bool calls_only) {
     d.rs_old = nrss ? (uint64_t*)w->rs_buf : nullptr;
     d.rs_new = nrss ? (uint64_t*)w->rs_buf + ngr : nullptr;
     d.rs_has = nrss ? (uint8_t*)w->rl_buf : nullptr;
+    RecHeads& rh = w->rheads;  // (re_old_h / re_new_h: after grow_rec_tiles, above)
+    rh.rs_bits_h = nrss && robj ? (const uint64_t*)(S + off_rbh) : nullptr;
+    rh.rs_old_h = nrss && robj ? (uint64_t*)w->rs_buf + 2 * ngr : nullptr;
+    rh.rs_new_h = nrss && robj ? (uint64_t*)w->rs_buf + 3 * ngr : nullptr;
+    rh.rc_bits_h = nrl && robj ? (const uint64_t*)(S + off_cbh) : nullptr;
+    rh.re_old_h = w->re_old_h;
+    rh.re_new_h = w->re_new_h;
     d.rss_ev = nrss ? (uint32_t*)w->rss_buf : nullptr;
     d.rss_msg = nrss ? (uint32_t*)w->rss_buf + nrss : nullptr;
     d.rss_pos = nrss ? (uint32_t*)w->rss_buf + 2 * nrss : nullptr;
@@ -4274,6 +4443,7 @@ static int execute_frame(World* w, int64_t now_ms, bool calls_only) {
     d.rl_cnt = nrl ? (uint32_t*)((char*)w->rl_buf + align16(std::max<size_t>(ngr, 1))) : nullptr;
     d.rl_ev = nrl ? d.rl_cnt + nrl : nullptr;
     w->rsq.clear();
+    w->rsq_h.clear();
     w->rvals.clear();
     w->rq_index.clear();
     w->ucache.clear();
@@ -4310,9 +4480,9 @@ static int execute_frame(World* w, int64_t now_ms, bool calls_only) {
             hipLaunchKernelGGL(k_rs_scatter, dim3((unsigned)((nrss + 255) / 256)), dim3(256), 0, w->stream,
                                d.rss_slot, (int32_t)nrss, d.rs_head);
             if (ngr)
-                hipLaunchKernelGGL(k_rsets, dim3((unsigned)((ngr + kTPB - 1) / kTPB)), dim3(kTPB), 0, w->stream, d);
+                hipLaunchKernelGGL(k_rsets, dim3((unsigned)((ngr + kTPB - 1) / kTPB)), dim3(kTPB), 0, w->stream, d, rh);
             if (nrl)  // after k_rsets: it clears the has-flags of the lists' groups
-                hipLaunchKernelGGL(k_rrows, dim3((unsigned)((nrl + kTPB - 1) / kTPB)), dim3(kTPB), 0, w->stream, d);
+                hipLaunchKernelGGL(k_rrows, dim3((unsigned)((nrl + kTPB - 1) / kTPB)), dim3(kTPB), 0, w->stream, d, rh);
         }
         if (ng) {
             // the device fold: keys (slot << 7 | property) -> stable radix sort -> groups
@@ -4627,7 +4797,8 @@ static int execute_frame(World* w, int64_t now_ms, bool calls_only) {
         constexpr int kWpb = kTPB / 64;  // record tiles (waves) per workgroup
         const dim3 g((unsigned)((d.n_rtiles + kWpb - 1) / kWpb)), b(kTPB);
         if (nrss)  // the SetRecord slots' events and messages, for k_records to reserve
-            hipLaunchKernelGGL((k_rset_slots<false>), dim3((unsigned)((nrss + kWpb - 1) / kWpb)), b, 0, w->stream, d);
+            hipLaunchKernelGGL((k_rset_slots<false>), dim3((unsigned)((nrss + kWpb - 1) / kWpb)), b, 0, w->stream, d,
+                               w->rheads);
         // (the SetRecord slots' instantiation, and the unfused one: the fast path stays lean)
         auto launch = [&](auto sets, auto fuse) {
             constexpr bool kS = decltype(sets)::value, kF = decltype(fuse)::value;
@@ -4658,7 +4829,8 @@ static int execute_frame(World* w, int64_t now_ms, bool calls_only) {
         else
             d.fuse_rec ? launch(F{}, T{}) : launch(F{}, F{});
         if (nrss)  // ... and written into the room k_records left
-            hipLaunchKernelGGL((k_rset_slots<true>), dim3((unsigned)((nrss + kWpb - 1) / kWpb)), b, 0, w->stream, d);
+            hipLaunchKernelGGL((k_rset_slots<true>), dim3((unsigned)((nrss + kWpb - 1) / kWpb)), b, 0, w->stream, d,
+                               w->rheads);
         HIPCHK(hipGetLastError());
     }
     if (nhq) {  // the post-scan entries (their count is the fold's, on the device)
@@ -4903,6 +5075,8 @@ int nfk_outputs_get(void* world, nfk_outputs* o) {
     o->slot_obj = w->slot_obj_d;
     o->ev_old_h = d.ev_old_h;
     o->ev_new_h = d.ev_new_h;
+    o->re_old_h = w->re_old_h;
+    o->re_new_h = w->re_new_h;
     return NFK_OK;
 }
 
@@ -5005,6 +5179,13 @@ int nfk_read_events(void* world, int32_t* ev_obj, int32_t* ev_pid, uint64_t* ev_
     return NFK_OK;
 }
 
+// whether a record event word (op << 24 | rec << 16 | row << 8 | col below the slot field) is the
+// Update of an object cell: the events whose head halves the device writes
+static bool rrc_obj_update(const World* w, uint32_t rrc) {
+    rrc &= kRrcHost;
+    return (rrc >> 24) == 0 && w->rec_ctype[(rrc >> 16) & 0xFF][rrc & 0xFF] == NFK_REC_OBJ_DATA;
+}
+
 int nfk_read_events_obj(void* world, uint64_t* ev_old_h, uint64_t* ev_new_h) {
     World* w = (World*)world;
     if (!w) return fail(NFK_ERR_ARG, "null world");
@@ -5048,6 +5229,29 @@ int nfk_read_rec_events(void* world, int32_t* re_obj, uint32_t* re_rrc, uint64_t
             re_obj[i] = w->obj_of_slot[(size_t)t * kRTile + (re_rrc[i] >> kRrcSitShift)];
             re_rrc[i] &= kRrcHost;
         }
+    return NFK_OK;
+}
+
+int nfk_read_rec_events_obj(void* world, uint64_t* re_old_h, uint64_t* re_new_h) {
+    World* w = (World*)world;
+    if (!w) return fail(NFK_ERR_ARG, "null world");
+    if (!w->committed) return fail(NFK_ERR_STATE, "commit first");
+    Ctrl c;
+    int r = read_ctrl(w, &c);
+    if (r) return r;
+    const Dev& d = w->d;
+    const size_t n = c.n_re;
+    if (!w->rec_obj) {
+        memset(re_old_h, 0, n * 8);
+        memset(re_new_h, 0, n * 8);
+        return NFK_OK;
+    }
+    std::vector<uint32_t> rrc(n);
+    GATHER(w, d.re_rrc, d.re_base, d.n_rtiles, d.re_tcap, n, rrc.data());
+    GATHER(w, w->re_old_h, d.re_base, d.n_rtiles, d.re_tcap, n, re_old_h);
+    GATHER(w, w->re_new_h, d.re_base, d.n_rtiles, d.re_tcap, n, re_new_h);
+    for (size_t i = 0; i < n; i++)  // (unwritten but for the Updates of object cells)
+        if (!rrc_obj_update(w, rrc[i])) re_old_h[i] = re_new_h[i] = 0;
     return NFK_OK;
 }
 
@@ -5204,6 +5408,8 @@ int nfk_read_frame(void* world, uint32_t what, nfk_frame_host* o) {
     const size_t o_eo = take(ne * 4), o_ep = take(ne * 4), o_eold = take(ne * 8), o_enew = take(ne * 8);
     const size_t o_eoh = take(heads ? ne * 8 : 0), o_enh = take(heads ? ne * 8 : 0);
     const size_t o_ro = take(nr * 4), o_rr = take(nr * 4), o_rold = take(nr * 8), o_rnew = take(nr * 8);
+    const bool rheads = events && w->rec_obj;  // (the object cells' head halves)
+    const size_t o_roh = take(rheads ? nr * 8 : 0), o_rnh = take(rheads ? nr * 8 : 0);
     const size_t o_fo = take(nf * 4), o_fk = take(nf * 4), o_fr = take(nf * 4);
     const size_t o_mo = take(fan ? (ne + nr + 1) * 4 : 0), o_mr = take(nm * 4);
     const size_t total = at;
@@ -5269,6 +5475,12 @@ int nfk_read_frame(void* world, uint32_t what, nfk_frame_host* o) {
                            d.re_base, d.n_rtiles, d.re_tcap);
         hipLaunchKernelGGL(k_compact<uint64_t>, dim3(grt), dim3(kTPB), 0, w->stream, d.re_new, (uint64_t*)(D + o_rnew),
                            d.re_base, d.n_rtiles, d.re_tcap);
+        if (rheads) {
+            hipLaunchKernelGGL(k_compact<uint64_t>, dim3(grt), dim3(kTPB), 0, w->stream, w->re_old_h,
+                               (uint64_t*)(D + o_roh), d.re_base, d.n_rtiles, d.re_tcap);
+            hipLaunchKernelGGL(k_compact<uint64_t>, dim3(grt), dim3(kTPB), 0, w->stream, w->re_new_h,
+                               (uint64_t*)(D + o_rnh), d.re_base, d.n_rtiles, d.re_tcap);
+        }
     }
     if (fan && ntt && nm == 0) {
         // (a frame without messages, e.g. Tutorial3's private World Sets: every offset is 0)
@@ -5336,6 +5548,14 @@ int nfk_read_frame(void* world, uint32_t what, nfk_frame_host* o) {
         o->re_rrc = (const uint32_t*)(H + o_rr);
         o->re_old = (const uint64_t*)(H + o_rold);
         o->re_new = (const uint64_t*)(H + o_rnew);
+        if (rheads) {  // (the device writes them for the Updates of object cells only: 0 elsewhere)
+            uint64_t* oh = (uint64_t*)(H + o_roh);
+            uint64_t* nh = (uint64_t*)(H + o_rnh);
+            for (size_t i = 0; i < nr; i++)
+                if (!rrc_obj_update(w, o->re_rrc[i])) oh[i] = nh[i] = 0;
+            o->re_old_h = oh;
+            o->re_new_h = nh;
+        }
     }
     if (fired) {
         o->fi_obj = (const int32_t*)(H + o_fo);
@@ -5757,7 +5977,24 @@ int nfk_jit_preview_rec(int32_t n_int, int32_t n_flt, int32_t n_class, int32_t n
             return fail(NFK_ERR_ARG, "bad record shape");
         tab->rec_rows[r] = rec_rows[r];
         tab->rec_cols[r] = rec_cols[r];
+        // the column types, as nfk_define_record checks them: an object column is a data half with
+        // its head half right behind it
+        for (int c = 0; col_types && c < rec_cols[r]; c++) {
+            const uint8_t* ct = col_types + (size_t)r * NFK_MAX_REC_COLS;
+            if (ct[c] > NFK_REC_OBJ_HEAD || (ct[c] == NFK_REC_OBJ_DATA && (c + 1 >= rec_cols[r] || ct[c + 1] != NFK_REC_OBJ_HEAD)) ||
+                (ct[c] == NFK_REC_OBJ_HEAD && (c == 0 || ct[c - 1] != NFK_REC_OBJ_DATA)))
+                return fail(NFK_ERR_ARG, "bad record column types");
+            tab->rec_ctype[r][c] = ct[c];
+        }
     }
+    for (int k = 0; k < n_kind; k++)  // a record op on a half of an object column, as nfk_define_kind refuses it
+        for (int i = 0; i < n_ops[k]; i++) {
+            const nfk_op& op = tab->ops[k][i];
+            if (op.code != NFK_OP_RIADD_CLAMP && op.code != NFK_OP_RFAFFINE) continue;
+            const int r = op.dst >> 8, col = op.dst & 255;
+            if (r < n_rec && col < rec_cols[r] && tab->rec_ctype[r][col] >= NFK_REC_OBJ_DATA)
+                return fail(NFK_ERR_ARG, "record op on a half of an object column");
+        }
     for (int k = 0; k < n_kind; k++)  // the guard cells, as nfk_define_kind checks them
         for (int i = 0; i < n_ops[k]; i++) {
             const nfk_op& op = tab->ops[k][i];

@@ -876,7 +876,21 @@ __global__ void k_rs_scatter(const uint32_t* __restrict__ rss_slot, int32_t n, u
     if (i < n) rs_head[rss_slot[i]] = (uint32_t)i + 1;  // 1 + the slot's index among the SetRecord slots
 }
 
-__global__ __launch_bounds__(kTPB) void k_rsets(Dev d) {
+// Object record cells (a world with an NFK_REC_OBJ_DATA column; null pointers otherwise): the NFGUID
+// head halves of the SetRecordObject calls, of their groups' frame-start / after values and of the
+// object cells' Update events (Dev's rs_bits / rc_bits / rs_old / rs_new / re_old / re_new hold the
+// data halves).  A second argument of the three SetRecord kernels, not part of Dev: k_tick and
+// k_records take Dev by value and stay the code they were.
+struct RecHeads {
+    const uint64_t* rs_bits_h;
+    const uint64_t* rc_bits_h;
+    uint64_t* rs_old_h;
+    uint64_t* rs_new_h;
+    uint64_t* re_old_h;
+    uint64_t* re_new_h;
+};
+
+__global__ __launch_bounds__(kTPB) void k_rsets(Dev d, RecHeads h) {
     const int g = blockIdx.x * kTPB + threadIdx.x;
     if (g >= d.n_rs) return;
     const uint32_t e = d.rs_slot[g], rrc = d.rs_rrc[g];
@@ -896,8 +910,37 @@ __global__ __launch_bounds__(kTPB) void k_rsets(Dev d) {
     uint64_t* cell = cells + ((size_t)e * cols + col) * rows + rec_pos(used, rec_rowm(rows), row);
     const uint64_t c0 = *cell;
     uint64_t v = c0;
+    const int ct = d.tab->rec_ctype[r][col];
+    if (ct == NFK_REC_OBJ_DATA) {
+        // NFCRecord::SetObject (RC:367-421): the NFGUID's head half at the same place of the next
+        // column vector; the cell changes when either half differs, both are written together
+        uint64_t* cellh = cell + rows;
+        const uint64_t h0 = *cellh;
+        uint64_t vh = h0;
+        if ((used >> row) & 1) {
+            bool logged = false;
+            for (uint32_t k = d.rs_first[g]; k < d.rs_first[g + 1]; k++) {
+                const uint64_t x = d.rs_bits[k], xh = h.rs_bits_h[k];
+                if (x != v || xh != vh) {
+                    v = x;
+                    vh = xh;
+                    logged = true;
+                }
+            }
+            if (v != c0 || vh != h0) {
+                *cell = v;
+                *cellh = vh;
+            }
+            d.rs_has[g] = logged ? 1 : 0;
+        }
+        d.rs_old[g] = c0;
+        d.rs_new[g] = v;
+        h.rs_old_h[g] = h0;
+        h.rs_new_h[g] = vh;
+        return;
+    }
     if ((used >> row) & 1) {
-        const bool f64 = d.tab->rec_ctype[r][col] != 0;
+        const bool f64 = ct == NFK_REC_F64;
         bool logged = false;
         for (uint32_t k = d.rs_first[g]; k < d.rs_first[g + 1]; k++) {
             const uint64_t x = d.rs_bits[k];
@@ -938,7 +981,7 @@ __device__ void rec_repack(uint64_t* cells, int rows, int cols, uint64_t rowm, u
     }
 }
 
-__global__ __launch_bounds__(kTPB) void k_rrows(Dev d) {
+__global__ __launch_bounds__(kTPB) void k_rrows(Dev d, RecHeads h) {
     const int l = blockIdx.x * kTPB + threadIdx.x;
     if (l >= d.n_rl) return;
     const uint32_t e = d.rl_slot[l];
@@ -968,8 +1011,24 @@ __global__ __launch_bounds__(kTPB) void k_rrows(Dev d) {
             const uint32_t g = d.rc_aux[k];
             uint64_t* c = cells + (size_t)col * rows + row;
             const uint64_t cur = *c, x = d.rc_bits[k];
+            const int ct = d.tab->rec_ctype[r][col];
+            if (ct == NFK_REC_OBJ_DATA) {  // SetObject: the pair (the head half in the next column's vector)
+                uint64_t* ch = c + rows;
+                const uint64_t curh = *ch, xh = h.rc_bits_h[k];
+                if (x == cur && xh == curh) continue;
+                if (!d.rs_has[g]) {
+                    d.rs_old[g] = cur;
+                    h.rs_old_h[g] = curh;
+                    d.rs_has[g] = 1;
+                }
+                d.rs_new[g] = x;
+                h.rs_new_h[g] = xh;
+                *c = x;
+                *ch = xh;
+                continue;
+            }
             bool changed;
-            if (d.tab->rec_ctype[r][col]) {
+            if (ct == NFK_REC_F64) {
                 const double df = __longlong_as_double((long long)x) - __longlong_as_double((long long)cur);
                 changed = !(df < 0.001 && df > -0.001);
             } else {
@@ -1022,7 +1081,7 @@ __global__ __launch_bounds__(kTPB) void k_rrows(Dev d) {
 // k_records, which reserves their room in the slot's place in its tile (rss_pos, rss_pmsg); kEmit:
 // write them there, with the cells' write-back and the fused fan-out, after it.
 template <bool kEmit>
-__global__ __launch_bounds__(kTPB) void k_rset_slots(Dev d) {
+__global__ __launch_bounds__(kTPB) void k_rset_slots(Dev d, RecHeads h) {
     __shared__ uint8_t s_rflags[NFK_MAX_CLASSES][NFK_MAX_RECORDS];
     for (int i = threadIdx.x; i < (int)sizeof(s_rflags) / 4; i += kTPB)
         ((uint32_t*)s_rflags)[i] = ((const uint32_t*)d.tab->rflags)[i];
@@ -1101,7 +1160,26 @@ __global__ __launch_bounds__(kTPB) void k_rset_slots(Dev d) {
             li++;
         }
         // cell (r, lane, c): its event (old, new) if any, and whether a record op writes nb back
-        auto eval = [&](int c, uint64_t& ob, uint64_t& nb, bool& wb) -> bool {
+        // (an object cell, at its data half's column: obj, with the head halves in obh / nbh — one
+        // event for the pair, none on the head column; record ops never target a half)
+        auto eval = [&](int c, uint64_t& ob, uint64_t& nb, bool& wb, bool& obj, uint64_t& obh, uint64_t& nbh) -> bool {
+            wb = false;
+            obj = false;
+            const int ct = d.tab->rec_ctype[r][c];
+            if (ct >= NFK_REC_OBJ_DATA) {
+                if (ct == NFK_REC_OBJ_HEAD || !act) return false;
+                int gi = -1;
+                const uint32_t key = ((uint32_t)r << 16) | ((uint32_t)lane << 8) | (uint32_t)c;
+                for (int g = g0; g < g1; g++)
+                    if ((d.rs_rrc[g] & 0x7FFFFFFFu) == key) gi = g;
+                if (gi < 0 || !d.rs_has[gi]) return false;
+                obj = true;
+                ob = d.rs_old[gi];
+                nb = d.rs_new[gi];
+                obh = h.rs_old_h[gi];
+                nbh = h.rs_new_h[gi];
+                return ob != nb || obh != nbh;
+            }
             bool op = false;
             int code = 0;
             int64_t oa = 0, obb = 0, oc = 0;
@@ -1151,18 +1229,18 @@ __global__ __launch_bounds__(kTPB) void k_rset_slots(Dev d) {
         };
         unsigned cnt = 0;
         for (int c = 0; c < cols; c++) {
-            uint64_t ob, nb;
-            bool wb;
-            cnt += eval(c, ob, nb, wb) ? 1u : 0u;
+            uint64_t ob, nb, obh, nbh;
+            bool wb, obj;
+            cnt += eval(c, ob, nb, wb, obj, obh, nbh) ? 1u : 0u;
         }
         const unsigned incl = wave_incl_scan_u32(cnt);
         const unsigned total = (unsigned)__builtin_amdgcn_readlane((int)incl, 63);
         if constexpr (kEmit) {
             unsigned k = incl - cnt;
             for (int c = 0; c < cols; c++) {
-                uint64_t ob, nb;
-                bool wb;
-                const bool ev = eval(c, ob, nb, wb);
+                uint64_t ob, nb, obh, nbh;
+                bool wb, obj;
+                const bool ev = eval(c, ob, nb, wb, obj, obh, nbh);
                 if (wb) {
                     __builtin_nontemporal_store(nb, cells + ((size_t)e * cols + c) * rows + lp);
                     bytes += 8;
@@ -1173,6 +1251,11 @@ __global__ __launch_bounds__(kTPB) void k_rset_slots(Dev d) {
                 d.re_rrc[re0 + at] = sit | ((uint32_t)r << 16) | ((uint32_t)lane << 8) | (uint32_t)c;
                 d.re_old[re0 + at] = ob;
                 d.re_new[re0 + at] = nb;
+                if (obj) {
+                    h.re_old_h[re0 + at] = obh;
+                    h.re_new_h[re0 + at] = nbh;
+                    bytes += 16;
+                }
                 if (!d.fuse_rec) d.re_moff[re0 + at] = lmo;  // tile-local: k_fanout adds the base
                 bytes += d.fuse_rec ? 20 : 24;
                 if (d.fuse_rec && per) fan(lmo);  // GetBroadCastObject (AOI:531-593)
@@ -2400,6 +2483,42 @@ __global__ __launch_bounds__(kTPB) void k_find_rows(const FindDev* __restrict__ 
             if ((used >> row) & 1) {
                 const uint64_t c = ((const uint64_t*)(uintptr_t)f.colv)[__builtin_popcountll(used & ((1ull << row) - 1))];
                 hit = f.flt ? __longlong_as_double((long long)c) == __longlong_as_double((long long)f.arg) : c == f.arg;
+            }
+        }
+    }
+    const unsigned long long b = __ballot(hit);
+    if (q < n && row == 0) masks[q] = (b >> (lane - row)) & rec_rowm(G);
+}
+
+// NFCRecord::FindObject (RC:957-987) of a batch (nfk_find_objects): k_find_rows' shape on an object
+// column, two adjacent column vectors (data half, then head half).  A used row's lane reads the data
+// word at place popcount(used & below) and the head word at the same place of the next vector, rows
+// words further; a row is a hit when both equal the argument's (NULL_OBJECT included: a used row
+// that holds (0, 0) is found).  The mask is one broadcast load per group; one ballot, the group's
+// first lane stores its G bits.  Every lane reaches the ballot; no atomics, no LDS.
+struct FindObjDev {
+    uint64_t used;   // absolute address of the used-row mask
+    uint64_t colv;   // absolute address of the data half's [rows] vector (the head half's follows it)
+    uint64_t arg_d;  // the argument's nData64
+    uint64_t arg_h;  // and nHead64
+    int32_t rows;
+    int32_t pad;
+};  // 40 bytes
+static_assert(sizeof(FindObjDev) == 40, "FindObjDev is 40 bytes");
+__global__ __launch_bounds__(kTPB) void k_find_objects(const FindObjDev* __restrict__ qs, int32_t n, int lg,
+                                                       uint64_t* __restrict__ masks) {
+    const int64_t t = (int64_t)blockIdx.x * kTPB + threadIdx.x;
+    const int64_t q = t >> lg;
+    const int lane = (int)(threadIdx.x & 63), G = 1 << lg, row = lane & (G - 1);
+    bool hit = false;
+    if (q < n) {  // (no early return: every lane of the wave takes part in the ballot)
+        const FindObjDev f = qs[q];
+        if (row < f.rows) {
+            const uint64_t used = *(const uint64_t*)(uintptr_t)f.used & rec_rowm(f.rows);
+            if ((used >> row) & 1) {
+                const uint64_t* p = (const uint64_t*)(uintptr_t)f.colv + __builtin_popcountll(used & ((1ull << row) - 1));
+                const uint64_t cd = p[0], ch = p[f.rows];  // (both loads issued before either compare)
+                hit = cd == f.arg_d && ch == f.arg_h;
             }
         }
     }

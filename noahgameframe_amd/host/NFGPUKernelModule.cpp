@@ -64,7 +64,18 @@ void NFGPUKernelModule::SetPropertyFlags(const std::string& cls, const std::stri
 }
 
 int NFGPUKernelModule::AddRecord(const std::string& name, int rows, const std::vector<TDATA_TYPE>& cols) {
-    records_.push_back({name, rows, cols});
+    // the logical <-> physical column map: an object column is its data half and its head half
+    RecordDef rd{name, rows, cols, {}, {}, 0};
+    for (size_t c = 0; c < cols.size(); c++) {
+        rd.phys.push_back(rd.pcols);
+        for (int k = 0; k < (cols[c] == TDATA_OBJECT ? 2 : 1); k++) rd.logical.push_back((int)c);
+        rd.pcols += cols[c] == TDATA_OBJECT ? 2 : 1;
+    }
+    if (rd.pcols > NFK_MAX_REC_COLS)
+        throw std::invalid_argument("AddRecord " + name + ": " + std::to_string(rd.pcols) +
+                                    " physical columns (an object column takes two), at most " +
+                                    std::to_string(NFK_MAX_REC_COLS));
+    records_.push_back(std::move(rd));
     record_id_[name] = (int)records_.size() - 1;
     return record_id_[name];
 }
@@ -248,7 +259,7 @@ bool NFGPUKernelModule::SetCreationRecord(const NFGUID& self, const std::string&
     const int o = ObjectIndex(self);
     if (committed_ || it == record_id_.end() || o < 0) return false;
     const RecordDef& rd = records_[it->second];
-    if (cells.size() != (size_t)rd.rows * rd.cols.size()) return false;
+    if (cells.size() != (size_t)rd.rows * (size_t)rd.pcols) return false;  // (physical columns)
     rec_init_[{o, it->second}] = {used & (rd.rows >= 64 ? ~0ull : ((1ull << rd.rows) - 1)), cells};
     return true;
 }
@@ -274,12 +285,19 @@ bool NFGPUKernelModule::AfterInit() {
     }
     for (int r = 0; r < (int)records_.size(); r++) {
         std::vector<uint8_t> ct, fl(classes_.size(), 0);
-        for (auto t : records_[r].cols) ct.push_back(t == TDATA_FLOAT ? 1 : 0);
+        for (auto t : records_[r].cols) {
+            if (t == TDATA_OBJECT) {
+                ct.push_back(NFK_REC_OBJ_DATA);
+                ct.push_back(NFK_REC_OBJ_HEAD);
+            } else {
+                ct.push_back(t == TDATA_FLOAT ? NFK_REC_F64 : NFK_REC_INT);
+            }
+        }
         for (int c = 0; c < (int)classes_.size(); c++) {
             auto it = classes_[c].record_flags.find(records_[r].name);
             if (it != classes_[c].record_flags.end()) fl[c] = it->second;
         }
-        check(nfk_define_record(world_, r, records_[r].rows, (int)records_[r].cols.size(), ct.data(), fl.data()),
+        check(nfk_define_record(world_, r, records_[r].rows, records_[r].pcols, ct.data(), fl.data()),
               "nfk_define_record");
     }
     // schedule names -> kind ids in lexical order (NFMapEx<std::string, NFCScheduleElement> order)
@@ -327,7 +345,7 @@ bool NFGPUKernelModule::AfterInit() {
         check(nfk_load_object(world_, PropertyId(props_[p].name), h.data(), d.data()), "nfk_load_object");
     }
     for (int r = 0; r < (int)records_.size(); r++) {  // creation-time record contents
-        const size_t per = (size_t)records_[r].rows * records_[r].cols.size();
+        const size_t per = (size_t)records_[r].rows * (size_t)records_[r].pcols;
         std::vector<uint64_t> cells(per * (size_t)n, 0), used((size_t)n, 0);
         bool any = false;
         for (auto& kv : rec_init_) {
@@ -786,7 +804,7 @@ bool NFGPUKernelModule::SetRecordInt(const NFGUID& self, const std::string& strR
     if (nRow < 0 || nRow >= rd.rows || nCol < 0 || nCol >= (int)rd.cols.size() || rd.cols[nCol] != TDATA_INT)
         return false;
     if (!((UsedRows(self, it->second) >> nRow) & 1)) return false;  // RC:194
-    const int32_t rec = it->second, row = nRow, col = nCol;
+    const int32_t rec = it->second, row = nRow, col = rd.phys[(size_t)nCol];
     const uint8_t f = 0;
     const uint64_t b = (uint64_t)nValue;
     if (nfk_set_records(world_, 1, &self.nHead64, &self.nData64, &rec, &row, &col, &f, &b) != NFK_OK) return false;
@@ -804,7 +822,7 @@ bool NFGPUKernelModule::SetRecordFloat(const NFGUID& self, const std::string& st
     if (nRow < 0 || nRow >= rd.rows || nCol < 0 || nCol >= (int)rd.cols.size() || rd.cols[nCol] != TDATA_FLOAT)
         return false;
     if (!((UsedRows(self, it->second) >> nRow) & 1)) return false;  // RC:255
-    const int32_t rec = it->second, row = nRow, col = nCol;
+    const int32_t rec = it->second, row = nRow, col = rd.phys[(size_t)nCol];
     const uint8_t f = 1;
     uint64_t b;
     memcpy(&b, &dwValue, 8);
@@ -812,6 +830,47 @@ bool NFGPUKernelModule::SetRecordFloat(const NFGUID& self, const std::string& st
     if (shard_) NoteCall(self);
     pending_calls_++;
     return true;
+}
+
+// NFCRecord::SetObject / GetObject (RC:367-421, RC:697-716); the entry points are looked up at first
+// use, like the finds' (nfgpu_symbol)
+bool NFGPUKernelModule::SetRecordObject(const NFGUID& self, const std::string& strRecordName, int nRow, int nCol,
+                                        const NFGUID& value) {
+    using Fn = int (*)(void*, int32_t, const int64_t*, const int64_t*, const int32_t*, const int32_t*, const int32_t*,
+                       const int64_t*, const int64_t*);
+    static const Fn fn = (Fn)nfgpu_symbol("nfk_set_record_objects");
+    if (!fn) throw std::runtime_error("nfk_set_record_objects: the nfgpu library has no such entry point");
+    Flush();  // (the buffered Set calls first: call order)
+    auto it = record_id_.find(strRecordName);
+    if (it == record_id_.end() || ObjectIndex(self) < 0) return false;
+    const RecordDef& rd = records_[it->second];
+    if (nRow < 0 || nRow >= rd.rows || nCol < 0 || nCol >= (int)rd.cols.size() || rd.cols[nCol] != TDATA_OBJECT)
+        return false;  // ValidPos and the column type (RC:369-377)
+    if (!((UsedRows(self, it->second) >> nRow) & 1)) return false;  // RC:379
+    const NFGUID cur = GetRecordObject(self, strRecordName, nRow, nCol);
+    if (cur.nHead64 == value.nHead64 && cur.nData64 == value.nData64) return false;  // RC:395
+    const int32_t rec = it->second, row = nRow, col = rd.phys[(size_t)nCol];
+    if (fn(world_, 1, &self.nHead64, &self.nData64, &rec, &row, &col, &value.nHead64, &value.nData64) != NFK_OK) return false;
+    if (shard_) NoteCall(self);
+    pending_calls_++;
+    return true;
+}
+
+NFGUID NFGPUKernelModule::GetRecordObject(const NFGUID& self, const std::string& strRecordName, int nRow, int nCol) {
+    using Fn = int (*)(void*, int32_t, const int64_t*, const int64_t*, const int32_t*, const int32_t*, const int32_t*,
+                       int64_t*, int64_t*);
+    static const Fn fn = (Fn)nfgpu_symbol("nfk_get_record_objects");
+    if (!fn) throw std::runtime_error("nfk_get_record_objects: the nfgpu library has no such entry point");
+    Flush();  // (the buffered Set calls first: call order)
+    auto it = record_id_.find(strRecordName);
+    if (it == record_id_.end() || ObjectIndex(self) < 0) return NFGUID();
+    const RecordDef& rd = records_[it->second];
+    if (nRow < 0 || nRow >= rd.rows || nCol < 0 || nCol >= (int)rd.cols.size() || rd.cols[nCol] != TDATA_OBJECT)
+        return NFGUID();
+    const int32_t rec = it->second, row = nRow, col = rd.phys[(size_t)nCol];
+    int64_t h = 0, d = 0;
+    if (fn(world_, 1, &self.nHead64, &self.nData64, &rec, &row, &col, &h, &d) != NFK_OK) return NFGUID();
+    return NFGUID(h, d);
 }
 
 uint64_t NFGPUKernelModule::UsedRows(const NFGUID& self, int rec) {
@@ -848,8 +907,15 @@ int NFGPUKernelModule::AddRow(const NFGUID& self, const std::string& strRecordNa
         nRow = __builtin_ctzll(fr);
     }
     uint64_t v[NFK_MAX_REC_COLS] = {};
-    for (size_t c = 0; c < values.size(); c++)
-        v[c] = rd.cols[c] == TDATA_INT ? (uint64_t)values[c].GetInt() : bits_of(values[c].GetFloat());
+    for (size_t c = 0; c < values.size(); c++) {
+        const size_t p = (size_t)rd.phys[c];
+        if (rd.cols[c] == TDATA_OBJECT) {  // data half, then head half
+            v[p] = (uint64_t)values[c].GetObject().nData64;
+            v[p + 1] = (uint64_t)values[c].GetObject().nHead64;
+        } else {
+            v[p] = rd.cols[c] == TDATA_INT ? (uint64_t)values[c].GetInt() : bits_of(values[c].GetFloat());
+        }
+    }
     const int32_t rec = it->second, op = 1, row = nRow;
     if (nfk_record_rows(world_, 1, &self.nHead64, &self.nData64, &rec, &op, &row, values.empty() ? nullptr : v) != NFK_OK)
         return -1;
@@ -890,7 +956,7 @@ int64_t NFGPUKernelModule::GetRecordInt(const NFGUID& self, const std::string& s
     if (it == record_id_.end() || ObjectIndex(self) < 0) return 0;
     const RecordDef& rd = records_[it->second];
     if (nRow < 0 || nRow >= rd.rows || nCol < 0 || nCol >= (int)rd.cols.size() || rd.cols[nCol] != TDATA_INT) return 0;
-    const int32_t rec = it->second, row = nRow, col = nCol;
+    const int32_t rec = it->second, row = nRow, col = rd.phys[(size_t)nCol];
     uint64_t b = 0;
     if (nfk_get_records(world_, 1, &self.nHead64, &self.nData64, &rec, &row, &col, &b) != NFK_OK) return 0;
     return (int64_t)b;
@@ -903,7 +969,7 @@ double NFGPUKernelModule::GetRecordFloat(const NFGUID& self, const std::string& 
     const RecordDef& rd = records_[it->second];
     if (nRow < 0 || nRow >= rd.rows || nCol < 0 || nCol >= (int)rd.cols.size() || rd.cols[nCol] != TDATA_FLOAT)
         return 0.0;
-    const int32_t rec = it->second, row = nRow, col = nCol;
+    const int32_t rec = it->second, row = nRow, col = rd.phys[(size_t)nCol];
     uint64_t b = 0;
     if (nfk_get_records(world_, 1, &self.nHead64, &self.nData64, &rec, &row, &col, &b) != NFK_OK) return 0.0;
     double v;
@@ -920,33 +986,57 @@ void NFGPUKernelModule::FindRows(const std::vector<RowFind>& finds, std::vector<
     if (!fn) throw std::runtime_error("nfk_find_rows: the nfgpu library has no such entry point");
     Flush();  // (the buffered Set calls first: call order)
     hits.assign(finds.size(), RowHits{});
-    std::vector<int64_t> gh, gd;
-    std::vector<int32_t> rec, col;
+    // the int / f64 finds go to nfk_find_rows, the NFGUID finds to nfk_find_objects: one call each
+    std::vector<int64_t> gh, gd, ogh, ogd, ovh, ovd;
+    std::vector<int32_t> rec, col, orec, ocol;
     std::vector<uint64_t> bits;
-    std::vector<size_t> at;
+    std::vector<size_t> at, oat;
     for (size_t i = 0; i < finds.size(); i++) {
         const RowFind& f = finds[i];
         auto it = record_id_.find(f.strRecordName);
         const TDATA_TYPE t = f.value.GetType();
-        // ValidCol and the column's type (RC:832-840, RC:875-883); "There is no object" (KM:487)
+        // ValidCol and the column's type (RC:832-840, RC:875-883, RC:959-967); "There is no object" (KM:487)
         if (!committed_ || it == record_id_.end() || ObjectIndex(f.self) < 0 || f.nCol < 0 ||
-            f.nCol >= (int)records_[it->second].cols.size() || (t != TDATA_INT && t != TDATA_FLOAT) ||
+            f.nCol >= (int)records_[it->second].cols.size() || (t != TDATA_INT && t != TDATA_FLOAT && t != TDATA_OBJECT) ||
             records_[it->second].cols[f.nCol] != t) {
             hits[i].invalid = true;
+            continue;
+        }
+        const int32_t pc = records_[it->second].phys[(size_t)f.nCol];
+        if (t == TDATA_OBJECT) {
+            ogh.push_back(f.self.nHead64);
+            ogd.push_back(f.self.nData64);
+            orec.push_back(it->second);
+            ocol.push_back(pc);
+            ovh.push_back(f.value.o.nHead64);
+            ovd.push_back(f.value.o.nData64);
+            oat.push_back(i);
             continue;
         }
         gh.push_back(f.self.nHead64);
         gd.push_back(f.self.nData64);
         rec.push_back(it->second);
-        col.push_back(f.nCol);
+        col.push_back(pc);
         bits.push_back(t == TDATA_INT ? (uint64_t)f.value.GetInt() : bits_of(f.value.GetFloat()));
         at.push_back(i);
     }
-    if (at.empty()) return;
-    std::vector<uint64_t> m(at.size());
-    check(fn(world_, (int32_t)at.size(), gh.data(), gd.data(), rec.data(), col.data(), bits.data(), m.data()),
-          "nfk_find_rows");
-    for (size_t j = 0; j < at.size(); j++) hits[at[j]].mask = m[j];
+    if (!at.empty()) {
+        std::vector<uint64_t> m(at.size());
+        check(fn(world_, (int32_t)at.size(), gh.data(), gd.data(), rec.data(), col.data(), bits.data(), m.data()),
+              "nfk_find_rows");
+        for (size_t j = 0; j < at.size(); j++) hits[at[j]].mask = m[j];
+    }
+    if (!oat.empty()) {
+        using FnO = int (*)(void*, int32_t, const int64_t*, const int64_t*, const int32_t*, const int32_t*, const int64_t*,
+                            const int64_t*, uint64_t*);
+        static const FnO fo = (FnO)nfgpu_symbol("nfk_find_objects");
+        if (!fo) throw std::runtime_error("nfk_find_objects: the nfgpu library has no such entry point");
+        std::vector<uint64_t> m(oat.size());
+        check(fo(world_, (int32_t)oat.size(), ogh.data(), ogd.data(), orec.data(), ocol.data(), ovh.data(), ovd.data(),
+                 m.data()),
+              "nfk_find_objects");
+        for (size_t j = 0; j < oat.size(); j++) hits[oat[j]].mask = m[j];
+    }
 }
 
 // ---- enter views (NFCGameServerNet_ServerModule.cpp:271-554) ----
@@ -991,11 +1081,13 @@ void NFGPUKernelModule::GetEnterViews(const std::vector<NFGUID>& objects, const 
             const size_t nu = (size_t)__builtin_popcountll(s.r_used[e]), nc = rd.cols.size();
             er.cells.resize(nu * nc);
             for (size_t k = 0; k < nu; k++)      // the device's column-major run as the reference's rows
-                for (size_t c = 0; c < nc; c++) {
-                    const uint64_t b = s.cells[(size_t)s.r_cell[e] + c * nu + k];
+                for (size_t c = 0; c < nc; c++) {  // (logical columns; the device's run holds physical ones)
+                    const size_t p = (size_t)rd.phys[c];
+                    const uint64_t b = s.cells[(size_t)s.r_cell[e] + p * nu + k];
                     TData& d = er.cells[k * nc + c];
                     d.type = rd.cols[c];
                     if (d.type == TDATA_INT) d.i = (int64_t)b;
+                    else if (d.type == TDATA_OBJECT) d.o = NFGUID((int64_t)s.cells[(size_t)s.r_cell[e] + (p + 1) * nu + k], (int64_t)b);
                     else memcpy(&d.f, &b, 8);
                 }
             v.records.push_back(std::move(er));
@@ -1068,7 +1160,18 @@ int NFGPUKernelModule::FindRowByColValue(const NFGUID& self, const std::string& 
     const TData* e = nCol >= 0 && (size_t)nCol < var.size() ? &var[(size_t)nCol] : nullptr;
     if (t == TDATA_INT) return FindInt(self, strRecordName, nCol, e ? e->GetInt() : 0, varResult);
     if (t == TDATA_FLOAT) return FindFloat(self, strRecordName, nCol, e ? e->GetFloat() : 0.0, varResult);
-    return -1;  // (string / object columns: device records hold none)
+    if (t == TDATA_OBJECT) return FindObject(self, strRecordName, nCol, e ? e->GetObject() : NFGUID(), varResult);  // RC:806
+    return -1;  // (string / vector columns: device records hold none)
+}
+
+int NFGPUKernelModule::FindObject(const NFGUID& self, const std::string& strRecordName, int nCol, const NFGUID& value,
+                                  std::vector<int>& varResult) {
+    TData v;
+    v.type = TDATA_OBJECT;
+    v.o = value;
+    std::vector<RowHits> h;
+    FindRows({RowFind{self, strRecordName, nCol, v}}, h);
+    return append_rows(h[0], varResult);
 }
 
 bool NFGPUKernelModule::QueryRow(const NFGUID& self, const std::string& strRecordName, int nRow,
@@ -1079,7 +1182,7 @@ bool NFGPUKernelModule::QueryRow(const NFGUID& self, const std::string& strRecor
     const RecordDef& rd = records_[it->second];
     if (nRow < 0 || nRow >= rd.rows) return false;                    // ValidRow (RC:556)
     if (!((UsedRows(self, it->second) >> nRow) & 1)) return false;  // IsUsed (RC:561)
-    const size_t nc = rd.cols.size();
+    const size_t nc = (size_t)rd.pcols;  // (the physical words of the row; a half is a word)
     std::vector<int64_t> gh(nc, self.nHead64), gd(nc, self.nData64);
     std::vector<int32_t> rec(nc, it->second), row(nc, nRow), col(nc);
     std::iota(col.begin(), col.end(), 0);
@@ -1087,11 +1190,13 @@ bool NFGPUKernelModule::QueryRow(const NFGUID& self, const std::string& strRecor
     check(nfk_get_records(world_, (int32_t)nc, gh.data(), gd.data(), rec.data(), row.data(), col.data(), b.data()),
           "nfk_get_records");
     varList.clear();
-    for (size_t c = 0; c < nc; c++) {
+    for (size_t c = 0; c < rd.cols.size(); c++) {
+        const size_t p = (size_t)rd.phys[c];
         TData v;
         v.type = rd.cols[c];
-        if (v.type == TDATA_INT) v.i = (int64_t)b[c];
-        else memcpy(&v.f, &b[c], 8);
+        if (v.type == TDATA_INT) v.i = (int64_t)b[p];
+        else if (v.type == TDATA_OBJECT) v.o = NFGUID((int64_t)b[p + 1], (int64_t)b[p]);  // one TDATA_OBJECT
+        else memcpy(&v.f, &b[p], 8);
         varList.push_back(v);
     }
     return true;
@@ -1719,14 +1824,22 @@ void NFGPUKernelModule::DeliverEvents(const nfk_frame_host& f, const NFGUID* ev_
         // row events (AddRow / Remove / Clear) carry empty values, as NFCRecord raises them (RC:177, 1098)
         ev.nOpType = op == 1 ? RECORD_EVENT_DATA::Add : op == 2 ? RECORD_EVENT_DATA::Del
                    : op == 3 ? RECORD_EVENT_DATA::Cover : RECORD_EVENT_DATA::Update;
+        // the event names the physical column (an object cell: its data half); callbacks get the logical one
+        const RecordDef& rd = records_[r];
+        const int lcol = op ? 0 : rd.logical[(size_t)col];
         ev.nRow = row;
-        ev.nCol = col;
+        ev.nCol = lcol;
         if (r != ev_r) {
-            ev.strRecordName = records_[r].name;
+            ev.strRecordName = rd.name;
             ev_r = r;
         }
         TData a, b;
-        TDataOf(op ? TDATA_UNKNOWN : records_[r].cols[col], f.re_old[e], f.re_new[e], &a, &b);
+        const TDATA_TYPE ct = op ? TDATA_UNKNOWN : rd.cols[(size_t)lcol];
+        TDataOf(ct, f.re_old[e], f.re_new[e], &a, &b);
+        if (ct == TDATA_OBJECT) {
+            a.o = NFGUID((int64_t)(f.re_old_h ? f.re_old_h[e] : 0), (int64_t)f.re_old[e]);
+            b.o = NFGUID((int64_t)(f.re_new_h ? f.re_new_h[e] : 0), (int64_t)f.re_new[e]);
+        }
         const NFGUID& self = re_self ? re_self[e] : guids_[f.re_obj[e]];
         for (auto& cb : common_rec_cb_) cb(self, ev, a, b);
         if (want_r) {  // (AOI.cpp:285-287 calls OnRecordEvent with an empty list too)

@@ -53,7 +53,7 @@ class Outputs(ctypes.Structure):
                 [(n, ctypes.c_void_p) for n in
                  ["ev_base", "fi_base", "re_base", "msg_base", "msg_cnt", "ev_slot", "ev_pid", "ev_old", "ev_new", "ev_moff",
                   "re_slot", "re_rrc", "re_old", "re_new", "re_moff", "fi_slot", "fi_kind", "fi_remain",
-                  "msg_rcpt", "slot_obj", "ev_old_h", "ev_new_h"]])
+                  "msg_rcpt", "slot_obj", "ev_old_h", "ev_new_h", "re_old_h", "re_new_h"]])
 
 
 class Query(ctypes.Structure):
@@ -79,6 +79,9 @@ class Snapshot(ctypes.Structure):
 
 
 VIEW_PUBLIC, VIEW_PRIVATE = 1, 2
+# record column types (NFK_REC_*): an object (NFGUID) column is a data half and its head half behind it
+REC_INT, REC_F64, REC_OBJ_DATA, REC_OBJ_HEAD = 0, 1, 2, 3
+REC_OBJECT = (REC_OBJ_DATA, REC_OBJ_HEAD)   # col_types.extend(REC_OBJECT): one logical object column
 MAX_RECORDS = 8   # NFK_MAX_RECORDS
 Q_PLAYERS, Q_OTHERS = 0, 1
 Q_ALL_GROUPS = 1
@@ -144,6 +147,10 @@ def load_library(path=LIB_PATH):
         "nfk_find_stats": [VP, VP, VP, VP], "nfk_get_used_rows": [VP, I32, VP, VP, VP, VP],
         "nfk_snapshot_objects": [VP, I32, VP, VP, VP, P(Snapshot)],
         "nfk_snapshot_objects_obj": [VP, I32, VP, VP, P(Snapshot)], "nfk_set_snapshot_order": [VP, VP, VP],
+        "nfk_set_record_objects": [VP, I32, VP, VP, VP, VP, VP, VP, VP],
+        "nfk_get_record_objects": [VP, I32, VP, VP, VP, VP, VP, VP, VP],
+        "nfk_find_objects": [VP, I32, VP, VP, VP, VP, VP, VP, VP],
+        "nfk_find_objects_obj": [VP, I32, VP, VP, VP, VP, VP, VP], "nfk_read_rec_events_obj": [VP, VP, VP],
     }
     for name, args in sig.items():
         if not hasattr(lib, name) and os.environ.get("NFGPU_LIB"):
@@ -202,6 +209,19 @@ class NFKernelModule:
         self._chk(self.lib.nfk_define_record(self.h, rec, rows, cols, _p(ct), _p(fl)))
         self.rec_shape[rec] = (cols, rows)
         self.rec_types = {**getattr(self, "rec_types", {}), rec: [int(t) for t in ct[:cols]]}
+        # the reference's LOGICAL columns (an object column is one) as physical columns: the C-ABI and
+        # the batch methods speak physical columns (an object cell named by its data half's), the
+        # methods with the reference's names (FindInt, SetRecordObject, QueryRow, ...) logical ones
+        self.rec_logical = {**getattr(self, "rec_logical", {}),
+                            rec: [c for c in range(cols) if int(ct[c]) != REC_OBJ_HEAD]}
+        self.rec_has_obj = getattr(self, "rec_has_obj", False) or REC_OBJ_DATA in self.rec_types[rec]
+
+    def _phys(self, rec, col):
+        """logical column -> (physical column, its type), or None for an unknown record / column"""
+        lg = getattr(self, "rec_logical", {}).get(rec)
+        if lg is None or col < 0 or col >= len(lg):
+            return None
+        return lg[col], self.rec_types[rec][lg[col]]
 
     def define_kind(self, kind, ops):
         ops = np.ascontiguousarray(ops)
@@ -304,6 +324,43 @@ class NFKernelModule:
         self.record_rows([guid[0]], [guid[1]], [rec], [3], [0])
         return True
 
+    # ---- NFIKernelModule::SetRecordObject / NFCRecord::GetObject (RC:367-421 / RC:697-716) ----
+    def set_record_objects(self, guid_head, guid_data, rec, row, col, val_head, val_data):
+        """nfk_set_record_objects: queued with set_records / record_rows in call order; col is the
+        physical column of the object cell's data half"""
+        a = [np.ascontiguousarray(x, t) for x, t in
+             ((guid_head, np.int64), (guid_data, np.int64), (rec, np.int32), (row, np.int32), (col, np.int32),
+              (val_head, np.int64), (val_data, np.int64))]
+        self._chk(self.lib.nfk_set_record_objects(self.h, len(a[0]), *[_p(x) for x in a]))
+
+    def get_record_objects(self, guid_head, guid_data, rec, row, col):
+        """nfk_get_record_objects -> (head, data) arrays, read-your-writes; (0, 0) for an unused row"""
+        a = [np.ascontiguousarray(x, t) for x, t in
+             ((guid_head, np.int64), (guid_data, np.int64), (rec, np.int32), (row, np.int32), (col, np.int32))]
+        vh = np.zeros(len(a[0]), np.int64)
+        vd = np.zeros(len(a[0]), np.int64)
+        self._chk(self.lib.nfk_get_record_objects(self.h, len(a[0]), *[_p(x) for x in a], _p(vh), _p(vd)))
+        return vh, vd
+
+    def SetRecordObject(self, guid, rec, row, col, value):
+        """NFIKernelModule::SetRecordObject (logical column): False for an unknown record, an invalid
+        row or column, or a column that holds no NFGUID (RC:367-381); the refusal on an unused row and
+        the equal-value test follow at the next frame, in call order"""
+        pc = self._phys(rec, col)
+        if pc is None or pc[1] != REC_OBJ_DATA or row < 0 or row >= self.rec_shape[rec][1]:
+            return False
+        self.set_record_objects([guid[0]], [guid[1]], [rec], [row], [pc[0]], [value[0]], [value[1]])
+        return True
+
+    def GetRecordObject(self, guid, rec, row, col):
+        """NFCRecord::GetObject (logical column) -> (head, data); NULL_OBJECT (0, 0) for an invalid
+        cell, a column of another type or an unused row"""
+        pc = self._phys(rec, col)
+        if pc is None or pc[1] != REC_OBJ_DATA or row < 0 or row >= self.rec_shape[rec][1]:
+            return 0, 0
+        vh, vd = self.get_record_objects([guid[0]], [guid[1]], [rec], [row], [pc[0]])
+        return int(vh[0]), int(vd[0])
+
     def get_records(self, guid_head, guid_data, rec, row, col):
         """NFIKernelModule::GetRecordInt/Float for n cells: raw 64-bit patterns, read-your-writes"""
         a = [np.ascontiguousarray(x, t) for x, t in
@@ -334,6 +391,42 @@ class NFKernelModule:
         self._find_stats(stats)
         return out
 
+    def find_objects(self, guid_head, guid_data, rec, col, val_head, val_data, stats=None):
+        """nfk_find_objects: n (object, record, object column, NFGUID) finds -> uint64 row masks (bit
+        r: row r is used and both halves of its cell equal the argument); col is the physical column
+        of the data half; read-your-writes and stats as find_rows"""
+        a = [np.ascontiguousarray(x, t) for x, t in
+             ((guid_head, np.int64), (guid_data, np.int64), (rec, np.int32), (col, np.int32), (val_head, np.int64),
+              (val_data, np.int64))]
+        out = np.zeros(len(a[0]), np.uint64)
+        self._chk(self.lib.nfk_find_objects(self.h, len(a[0]), *[_p(x) for x in a], _p(out)))
+        self._find_stats(stats)
+        return out
+
+    def find_objects_obj(self, obj, rec, col, val_head, val_data, stats=None):
+        """nfk_find_objects_obj: find_objects by object index"""
+        a = [np.ascontiguousarray(x, t) for x, t in
+             ((obj, np.int32), (rec, np.int32), (col, np.int32), (val_head, np.int64), (val_data, np.int64))]
+        out = np.zeros(len(a[0]), np.uint64)
+        self._chk(self.lib.nfk_find_objects_obj(self.h, len(a[0]), *[_p(x) for x in a], _p(out)))
+        self._find_stats(stats)
+        return out
+
+    def FindObject(self, guid, rec, col, value, result):
+        """NFCRecord::FindObject (RC:957, logical column): rows whose cell equals the NFGUID value
+        (head, data), appended to result; -1 as FindInt"""
+        pc = self._phys(rec, col)
+        if pc is None or pc[1] != REC_OBJ_DATA:
+            return -1
+        try:
+            m = int(self.find_objects([guid[0]], [guid[1]], [rec], [pc[0]], [value[0]], [value[1]])[0])
+        except NFKError as e:
+            if e.code != -7:
+                raise
+            return -1
+        result.extend(r for r in range(64) if (m >> r) & 1)
+        return len(result)
+
     def _find_stats(self, stats):
         if stats is None:
             return
@@ -344,12 +437,10 @@ class NFKernelModule:
     def _find(self, guid, rec, col, bits, want_float, result):
         """the reference's return: -1 (nothing appended) for an unknown object or record, an invalid
         column or a column of another type; else the hits appended and result's total size (RC:856)"""
-        shape = self.rec_shape.get(rec)
-        types = getattr(self, "rec_types", {}).get(rec)
-        if shape is None or col < 0 or col >= shape[0]:
+        pc = self._phys(rec, col)   # (logical column; an object column is a column of another type)
+        if pc is None or pc[1] != (REC_F64 if want_float else REC_INT):
             return -1
-        if types is not None and bool(types[col]) != want_float:
-            return -1
+        col = pc[0]
         try:
             m = int(self.find_rows([guid[0]], [guid[1]], [rec], [col], [bits])[0])
         except NFKError as e:
@@ -369,7 +460,8 @@ class NFKernelModule:
 
     def QueryRow(self, guid, rec, row):
         """NFCRecord::QueryRow (RC:554): the row's cells as raw 64-bit patterns [cols], or None for
-        an invalid or unused row (the reference's false)"""
+        an invalid or unused row (the reference's false).  A record with object columns answers a
+        list over its logical columns, an object cell as its (head, data) pair."""
         shape = self.rec_shape.get(rec)
         if shape is None or row < 0 or row >= shape[1]:
             return None
@@ -379,7 +471,12 @@ class NFKernelModule:
         if not (int(used[0]) >> row) & 1:
             return None
         cols = shape[0]
-        return self.get_records([guid[0]] * cols, [guid[1]] * cols, [rec] * cols, [row] * cols, list(range(cols)))
+        w = self.get_records([guid[0]] * cols, [guid[1]] * cols, [rec] * cols, [row] * cols, list(range(cols)))
+        types = self.rec_types[rec]
+        if REC_OBJ_DATA not in types:
+            return w
+        return [(int(w[c + 1].view(np.int64)), int(w[c].view(np.int64))) if types[c] == REC_OBJ_DATA else w[c]
+                for c in self.rec_logical[rec]]
 
     # ---- enter snapshots: OnPropertyEnter / OnRecordEnter payloads (nfk_snapshot_objects) ----
     def set_snapshot_order(self, prop_order=None, rec_order=None):
@@ -433,11 +530,25 @@ class NFKernelModule:
         self._chk(self.lib.nfk_snapshot_objects_obj(self.h, len(o), _p(o), _p(v), ctypes.byref(res)))
         return self._snapshot_arrays(res, len(o), stats)
 
+    def _set_col(self, rec, col):
+        """the physical column of a SetRecordInt / SetRecordFloat's logical column, or None when it is
+        an object column (a column of another type: the reference returns false, RC:189)"""
+        pc = self._phys(rec, col)
+        if pc is None:
+            return col   # (an unknown record or column: nfk_set_records reports it)
+        return None if pc[1] >= REC_OBJ_DATA else pc[0]
+
     def SetRecordInt(self, guid, rec, row, col, value):
+        col = self._set_col(rec, col)
+        if col is None:
+            return False
         self.set_records([guid[0]], [guid[1]], [rec], [row], [col], [np.int64(value).view(np.uint64)], [0])
         return True
 
     def SetRecordFloat(self, guid, rec, row, col, value):
+        col = self._set_col(rec, col)
+        if col is None:
+            return False
         self.set_records([guid[0]], [guid[1]], [rec], [row], [col], [np.float64(value).view(np.uint64)], [1])
         return True
 
@@ -738,6 +849,10 @@ class NFKernelModule:
             oh = [np.zeros(ne, np.uint64), np.zeros(ne, np.uint64)]
             self._chk(self.lib.nfk_read_events_obj(self.h, *[_p(x) for x in oh]))
             out["ev_oldh"], out["ev_newh"] = oh
+        if getattr(self, "rec_has_obj", False):   # the object cells' Update events: their head halves
+            rh = [np.zeros(nr, np.uint64), np.zeros(nr, np.uint64)]
+            self._chk(self.lib.nfk_read_rec_events_obj(self.h, *[_p(x) for x in rh]))
+            out["re_oldh"], out["re_newh"] = rh
         return out
 
     # ---- per-Set chains (NFIKernelModule::AddPropertyCallBack) ----
