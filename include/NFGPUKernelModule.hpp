@@ -439,6 +439,13 @@ public:
     int AddRow(const NFGUID& self, const std::string& strRecordName, int nRow, const std::vector<TData>& values = {});
     bool RemoveRow(const NFGUID& self, const std::string& strRecordName, int nRow);
     bool ClearRecord(const NFGUID& self, const std::string& strRecordName);
+    // NFCRecord::SwapRowInfo (RC:1219-1253): the reference's return value — false for an unknown object
+    // or record, a row outside the record, or an origin row that is unused now (the window's queued
+    // calls replayed); true once queued.  A used origin changes places with the target row: the cells
+    // of every column, the used states (an unused target: a move) and the window's Update log.  One
+    // record event with the frame: nOpType = Swap, nRow = origin, nCol = target ROW, empty values.
+    // The entry point is looked up at first use; a library without it: std::runtime_error.
+    bool SwapRowInfo(const NFGUID& self, const std::string& strRecordName, int nOriginRow, int nTargetRow);
     bool IsUsed(const NFGUID& self, const std::string& strRecordName, int nRow);
     // NFIKernelModule::GetRecordInt / GetRecordFloat (NFIKernelModule.h:134-135): read-your-writes
     // like GetProperty*; 0 for an unused row (NFCRecord::GetInt, RC:623)

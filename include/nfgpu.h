@@ -170,10 +170,14 @@ typedef struct nfk_summary {
  *   record events    (scene, group, guid, rec, ...): per record its row events (AddRow / Remove /
  *                    ClearRecord, in call order) then its cell Updates in (row, col) order;
  *                    rrc = op<<24 | rec<<16 | row<<8 | col, op 0 = Update (RECORD_EVENT_DATA::Update,
- *                    old / new the cell), 1 = Add, 2 = Del, 3 = Cover (row events: col 0, old = new = 0).
+ *                    old / new the cell), 1 = Add, 2 = Del, 3 = Cover (row events: col 0, old = new = 0),
+ *                    4 = Swap (nfk_swap_rows; a row event: the row field the origin row, the col
+ *                    field the TARGET ROW, old = new = 0).
  *                    In the raw tiles (nfk_outputs) the word also carries the event's slot: bits
  *                    26-31 = slot - tile * rtile_slots (the record tile the event sits in), op in
- *                    bits 24-25; re_slot is NULL.  The nfk_read_* arrays carry the word above.
+ *                    bits 24-25; re_slot is NULL.  A Swap's raw word has op bits 0 and bit 23 set
+ *                    (rec needs bits 16-18 only): slot << 26 | 1 << 23 | rec << 16 | origin << 8 |
+ *                    target.  The nfk_read_* arrays carry the word above (a Swap: 4 << 24 | ...).
  *   fired heartbeats (scene, group, guid, kind)
  * Fan-out (GetBroadCastObject recipients): the messages of tile t (property tiles, then record
  * tiles) are one run of msg_cnt[t] recipients at msg_rcpt[msg_base[t]], in event order.  Runs
@@ -349,6 +353,25 @@ int nfk_set_record_objects(void* world, int32_t n, const int64_t* guid_head, con
  * NFK_ERR_NOTFOUND for an unknown GUID, NFK_ERR_ARG for a row outside the record. */
 int nfk_record_rows(void* world, int32_t n, const int64_t* guid_head, const int64_t* guid_data, const int32_t* rec,
                     const int32_t* op, const int32_t* row, const uint64_t* values);
+
+/* NFCRecord::SwapRowInfo(origin, target) (RC:1219-1253), queued in call order WITH the window's
+ * nfk_set_records / nfk_set_record_objects / nfk_record_rows calls on the same (object, record) and
+ * applied at the start of the next frame.  An origin unused at that point of the call order: nothing
+ * happens and no event is raised.  Otherwise the two rows' cells are exchanged in every physical
+ * column (both halves of an object column; whatever an unused target still holds travels too) and
+ * the two used bits are exchanged, so a used origin and an unused target is a move.  origin ==
+ * target on a used row changes nothing and raises the event.  One Swap event per accepted call
+ * (rrc = 4 << 24 | rec << 16 | origin << 8 | target, old = new = 0; see nfk_outputs), delivered with
+ * the record's other row events in call order, ahead of its cell Updates, to the recipients of any
+ * event of that record; no Update is raised for a moved cell.
+ * Coalescing: the frame's one Update per cell (first logged old value to last logged new one) FOLLOWS
+ * THE ROW: a Swap of rows a, b re-keys every log entry made before it on a row a cell to row b and
+ * the other way round.  Set(a, c) v0 -> v1 then Swap(a, b) yields Swap(a, b), Update(b, c) v0 -> v1:
+ * a client that applies the frame's events in order ends in the server's state.
+ * NFK_ERR_STATE before commit, NFK_ERR_NOTFOUND for an unknown GUID, NFK_ERR_ARG for a bad record or
+ * a row outside [0, rows); a failed batch queues nothing. */
+int nfk_swap_rows(void* world, int32_t n, const int64_t* guid_head, const int64_t* guid_data, const int32_t* rec,
+                  const int32_t* row_origin, const int32_t* row_target);
 
 /* NFCRecord::IsUsed (RC:1209) for n (object, record) pairs: the used-row masks as the reference holds
  * them now — the device's after the last frame (one read per pair per window, cached until the next

@@ -18,8 +18,15 @@ static_assert(kRTile >= 1 && kRTile <= 64, "a record tile is at most one wave of
 // row-event op (0 a cell's update, 1 AddRow, 2 Remove, 3 Clear / Cover) in bits 24-25, and the slot's
 // index within its record tile in bits 26-31 (the tile is where the event sits), so no slot word is
 // stored per event.  The host formats carry op << 24 | record << 16 | row << 8 | column.
+// A Swap (op 4, NFCRecord::SwapRowInfo) does not fit the two op bits: its raw word is kRrcSwap |
+// record << 16 | origin row << 8 | target row with op bits 0 (a record index needs bits 16-18
+// only), and rrc_host turns it into the host's 4 << 24 | record << 16 | origin << 8 | target.
 constexpr uint32_t kRrcHost = 0x03FFFFFFu;
 constexpr int kRrcSitShift = 26;
+constexpr uint32_t kRrcSwap = 1u << 23;
+__host__ __device__ __forceinline__ uint32_t rrc_host(uint32_t x) {
+    return (x & kRrcHost & ~kRrcSwap) | ((x & kRrcSwap) << 3);
+}
 
 // device error word bits (Ctrl::err); kErrRemain: a fired heartbeat's remain was read from an LDS slot
 // this launch never wrote (only with kAblCheckRem)
@@ -249,7 +256,8 @@ struct Dev {
     // record row operations (NFCRecord::AddRow / Remove, NFCKernelModule::ClearRecord) of this window:
     // one LIST per (slot, record) with row operations, sorted by (slot, record); a list's calls (its
     // row operations and that pair's SetRecord calls) in call order.  k_rrows runs each list; its row
-    // events (op << 8 | row) go to rl_ev[rl_ev0[l] ...], rl_cnt[l] of them.
+    // events (op << 8 | row; a Swap: 4 << 8 | origin | target << 16) go to rl_ev[rl_ev0[l] ...],
+    // rl_cnt[l] of them.
     int32_t n_rl;
     const uint32_t* rl_slot;
     const uint32_t* rl_rec;
@@ -257,8 +265,11 @@ struct Dev {
     const uint32_t* rl_ev0;
     uint32_t* rl_cnt;
     uint32_t* rl_ev;
-    const uint32_t* rc_code;   // op | row << 8 | col << 16 (op 0 SetRecord, 1 AddRow (row 0xFF: -1), 2 Remove, 3 Clear)
-    const uint32_t* rc_aux;    // SetRecord: its group; AddRow: its values' index (0xFFFFFFFF: the initial 0s)
+    const uint32_t* rc_code;   // op | row << 8 | col << 16 (op 0 SetRecord, 1 AddRow (row 0xFF: -1), 2 Remove, 3 Clear,
+                               // 4 SwapRowInfo: row the origin, the col field the target row)
+    const uint32_t* rc_aux;    // SetRecord: its group; AddRow: its values' index (0xFFFFFFFF: the initial 0s);
+                               // Swap: the first of the group pairs whose logs travel with its rows (rc_bits:
+                               // how many), in RecHeads::rs_swap
     const uint64_t* rc_bits;   // SetRecord: the value
     const uint64_t* rvals;     // AddRow values [][NFK_MAX_REC_COLS]
     const uint32_t* rss_l0;    // [n_rss] the slot's first list

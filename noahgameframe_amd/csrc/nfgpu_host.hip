@@ -226,7 +226,7 @@ struct World {
     // queued SetRecordInt / SetRecordFloat calls (obj: object index until nfk_execute resolves it;
     // rrc = rec << 16 | row << 8 | col) and their folding scratch
     // op 0 SetRecord*, 1 AddRow (row 0xFF: -1; aux = its values' index in rvals, or 0xFFFFFFFF),
-    // 2 Remove, 3 ClearRecord
+    // 2 Remove, 3 ClearRecord, 4 SwapRowInfo (row the origin, the col field the target row)
     struct RSOp { uint32_t obj, rrc; uint64_t bits; uint32_t op, aux; };
     std::vector<RSOp> rsq;
     // the NFGUID head halves of the queued SetRecordObject calls (bits: the data halves), parallel
@@ -2566,6 +2566,34 @@ int nfk_record_rows(void* world, int32_t n, const int64_t* gh, const int64_t* gd
     return NFK_OK;
 }
 
+// NFCRecord::SwapRowInfo (RC:1219-1253), queued with the record's other calls (World::rsq, op 4: the
+// row field the origin, the col field the target row)
+int nfk_swap_rows(void* world, int32_t n, const int64_t* gh, const int64_t* gd, const int32_t* rec,
+                  const int32_t* row_origin, const int32_t* row_target) {
+    World* w = (World*)world;
+    if (!w || n < 0 || (n && (!gh || !gd || !rec || !row_origin || !row_target))) return fail(NFK_ERR_ARG, "null argument");
+    if (!w->committed) return fail(NFK_ERR_STATE, "commit first");
+    w->look.resize(n);
+    if (int rl = find_many_par(w, n, gh, gd, w->look.data())) return rl;
+    for (int32_t i = 0; i < n; i++) {
+        if (w->look[i] < 0)  // FindRecord: "There is no object" (KM:487)
+            return fail(NFK_ERR_NOTFOUND, "no object " + std::to_string(gh[i]) + "-" + std::to_string(gd[i]));
+        const int32_t r = rec[i];
+        if (r < 0 || r >= w->cfg.n_rec || !w->rec_defined[r]) return fail(NFK_ERR_ARG, "bad record");
+        if (row_origin[i] < 0 || row_origin[i] >= w->tab.rec_rows[r] || row_target[i] < 0 ||
+            row_target[i] >= w->tab.rec_rows[r])
+            return fail(NFK_ERR_ARG, "row out of range");
+    }
+    w->rsq.reserve(w->rsq.size() + n);
+    for (int32_t i = 0; i < n; i++) {
+        w->rq_index[((uint64_t)w->look[i] << 3) | (uint32_t)rec[i]].push_back((uint32_t)w->rsq.size());
+        w->rsq.push_back(World::RSOp{(uint32_t)w->look[i],
+                                     ((uint32_t)rec[i] << 16) | ((uint32_t)row_origin[i] << 8) | (uint32_t)row_target[i], 0ull,
+                                     4u, 0u});
+    }
+    return NFK_OK;
+}
+
 // device address of object o's used-row mask of record r (its import row in this window, or its slot)
 static int used_addr(World* w, int32_t o, int32_t r, const uint64_t** used) {
     const int rows = w->tab.rec_rows[r], cols = w->tab.rec_cols[r];
@@ -2620,6 +2648,9 @@ static uint64_t replay_rows(const World* w, int32_t o, int32_t r, uint64_t u) {
             u &= ~(1ull << xr);
         } else if (x.op == 3) {
             u = 0;
+        } else if (x.op == 4) {  // SwapRowInfo: a used origin's bit and the target's change places
+            const int xt = (int)(x.rrc & 0xFF);
+            if ((u >> xr) & 1) u = (u & ~(1ull << xr)) | (((u >> xt) & 1) << xr) | (1ull << xt);
         }
     }
     return u;
@@ -2661,8 +2692,11 @@ int nfk_get_used_rows(void* world, int32_t n, const int64_t* gh, const int64_t* 
 // This window's queued calls on (object o, record r) replayed in call order on its used-row mask u
 // and on column col's cells c[rows] in ROW order: SetRecord* through RC:182 / RC:243 on the row's
 // used state at that call, AddRow / Remove / ClearRecord on the mask (RC:111, RC:1086, RC:1109).  A
-// Remove leaves the cell's value behind (RC:1086-1107); an AddRow without values writes 0.  A row's
-// result depends on no other row's cell.  Shared by nfk_get_records and nfk_find_rows.
+// Remove leaves the cell's value behind (RC:1086-1107); an AddRow without values writes 0.  A
+// SwapRowInfo of a used origin exchanges the two rows' cells and used bits (RC:1219-1253), so a
+// row's result depends on other rows' cells: a caller hands in the cells of every row the device
+// holds as used whenever the list holds a Swap (list_swaps).  Shared by nfk_get_records and
+// nfk_find_rows.
 // The pair form (ch != null, col the data half of an object column): c the data halves, ch the head
 // halves; SetRecordObject writes both (RC:367-421), AddRow both words of its values.  Without ch a
 // half column replays as the word it is (nfk_get_records): a queued SetRecordObject is named by its
@@ -2704,10 +2738,23 @@ static void replay_column(const World* w, int32_t o, int32_t r, int32_t col, uin
             if (ch) ch[rr] = x.aux == 0xFFFFFFFFu ? 0ull : w->rvals[(size_t)x.aux * NFK_MAX_REC_COLS + col + 1];
         } else if (x.op == 2) {
             u &= ~(1ull << xr);
-        } else {
+        } else if (x.op == 3) {
             u = 0;
+        } else if ((u >> xr) & 1) {  // SwapRowInfo (the col field: the target row)
+            std::swap(c[xr], c[xc]);
+            if (ch) std::swap(ch[xr], ch[xc]);
+            u = (u & ~(1ull << xr)) | (((u >> xc) & 1) << xr) | (1ull << xc);
         }
     }
+}
+
+// whether the window's queued calls on (object o, record r) hold a SwapRowInfo
+static bool list_swaps(const World* w, int32_t o, int32_t r) {
+    auto it = w->rq_index.find(((uint64_t)o << 3) | (uint32_t)r);
+    if (it == w->rq_index.end()) return false;
+    for (uint32_t k : it->second)
+        if (w->rsq[k].op == 4) return true;
+    return false;
 }
 
 // nfk_get_records (heads null: the cells as the words they are) and nfk_get_record_objects (heads:
@@ -2729,7 +2776,10 @@ static int get_record_cells(World* w, int32_t n, const int64_t* gh, const int64_
     // every query's used-row mask (this window's cache, else one gather), then the cells of the
     // rows the device holds as used in a second: a cell's place in its vector follows from the
     // mask (rec_pos); a row the device holds unused reads 0 unless a queued AddRow writes it
-    std::vector<uint64_t> um(n), cv(n, 0), hv(heads ? n : 0, 0);
+    std::vector<uint64_t> um(n), cv(n, 0), hv(heads ? n : 0, 0), swv;
+    std::vector<uint8_t> swl(n, 0);   // the query's list holds a SwapRowInfo (list_swaps)
+    std::vector<size_t> sw_at(n, 0);  // such a query's cells in swv
+    for (int32_t i = 0; i < n; i++) swl[i] = list_swaps(w, obj[i], rec[i]);
     {
         std::vector<uint64_t> addr;
         std::vector<int32_t> miss;
@@ -2756,8 +2806,10 @@ static int get_record_cells(World* w, int32_t n, const int64_t* gh, const int64_
         std::vector<int32_t> at;
         for (int32_t i = 0; i < n; i++) {
             const int32_t o = obj[i], r = rec[i], rows = w->tab.rec_rows[r], cols = w->tab.rec_cols[r];
-            if (!((um[i] >> row[i]) & 1)) continue;
-            const size_t place = (size_t)col[i] * rows + rec_pos(um[i], rec_rowm(rows), row[i]);
+            // a list with a SwapRowInfo: the cell may come from any row, so every used row's is read
+            const bool sw = swl[i];
+            if (sw ? !(um[i] & rec_rowm(rows)) : !((um[i] >> row[i]) & 1)) continue;
+            const size_t place = (size_t)col[i] * rows + (sw ? 0 : rec_pos(um[i], rec_rowm(rows), row[i]));
             const uint64_t* cell;
             if (w->src_row[o] >= 0) {  // entered in this window: its row of the import buffer
                 int64_t off = w->n_pw + 4 * w->cfg.n_kind;
@@ -2768,21 +2820,42 @@ static int get_record_cells(World* w, int32_t n, const int64_t* gh, const int64_
             } else {
                 return fail(NFK_ERR_STATE, "object without a slot");
             }
-            addr.push_back((uint64_t)(uintptr_t)cell);
-            if (heads) addr.push_back((uint64_t)(uintptr_t)(cell + rows));  // (the same place of the next column vector)
+            // (the used rows first, in row order: rec_pos; a pair's head half at the same place of the next vector)
+            const int np = sw ? __builtin_popcountll(um[i] & rec_rowm(rows)) : 1;
+            for (int p = 0; p < np; p++) {
+                addr.push_back((uint64_t)(uintptr_t)(cell + p));
+                if (heads) addr.push_back((uint64_t)(uintptr_t)(cell + p + rows));
+            }
             at.push_back(i);
         }
         std::vector<uint64_t> got(addr.size());
         if (int r = read_abs(w, addr, got.data())) return r;
+        size_t g = 0;
         for (size_t q = 0; q < at.size(); q++) {
-            cv[at[q]] = got[heads ? 2 * q : q];
-            if (heads) hv[at[q]] = got[2 * q + 1];
+            const int32_t i = at[q];
+            if (swl[i]) {
+                sw_at[i] = g;
+                g += (size_t)__builtin_popcountll(um[i] & rec_rowm(w->tab.rec_rows[rec[i]])) * (heads ? 2 : 1);
+                continue;
+            }
+            cv[i] = got[g++];
+            if (heads) hv[i] = got[g++];
         }
+        swv.swap(got);
     }
     for (int32_t i = 0; i < n; i++) {
         uint64_t u = um[i], c[64] = {}, ch[64] = {};
-        c[row[i]] = cv[i];
-        if (heads) ch[row[i]] = hv[i];
+        if (swl[i]) {
+            size_t g = sw_at[i];
+            for (int rr = 0; rr < w->tab.rec_rows[rec[i]]; rr++)
+                if ((u >> rr) & 1) {
+                    c[rr] = swv[g++];
+                    if (heads) ch[rr] = swv[g++];
+                }
+        } else {
+            c[row[i]] = cv[i];
+            if (heads) ch[row[i]] = hv[i];
+        }
         replay_column(w, obj[i], rec[i], col[i], u, c, heads ? ch : nullptr);
         // NFCRecord::GetInt / GetFloat / GetObject of an unused row (RC:623, RC:704): 0 / NULL_OBJECT
         bits[i] = ((u >> row[i]) & 1) ? c[row[i]] : 0;
@@ -4118,11 +4191,14 @@ static int execute_frame(World* w, int64_t now_ms, bool calls_only) {
     const uint64_t rim = (1ull << rib) - 1;
     int64_t max_rs_tile = 0;
     size_t n_rev = 0;  // row-event bound of the window
+    bool any_swap = false;
+    std::vector<uint32_t> rs_swap;  // the group pairs the window's Swaps exchange (RecHeads::rs_swap)
     if (n_rq) {
         for (size_t i = 0; i < n_rq; i++)
             if (w->rsq[i].op) {
                 const int32_t sl = w->slot_of_obj[w->rsq[i].obj];
                 if (sl >= 0) rowpairs.push_back(((uint64_t)(uint32_t)sl << 3) | (w->rsq[i].rrc >> 16));
+                any_swap = any_swap || (sl >= 0 && w->rsq[i].op == 4);
             }
         std::sort(rowpairs.begin(), rowpairs.end());
         rowpairs.erase(std::unique(rowpairs.begin(), rowpairs.end()), rowpairs.end());
@@ -4156,7 +4232,80 @@ static int execute_frame(World* w, int64_t now_ms, bool calls_only) {
             rs_rrc.push_back(rrc | (pair_of(sl, rrc >> 16) >= 0 ? 0x80000000u : 0u));
             rs_first.push_back((uint32_t)i);
         }
+        // SwapRowInfo: the window's Update log follows the row, so k_rrows exchanges the two rows'
+        // groups with their cells.  A cell without a queued Set gets a group (no calls, rs_rrc bit
+        // 31) when a Swap can hand it the other row's log: per list in call order, whenever one of
+        // (origin, c) and (target, c) has a group the other gets one, closed over chains of swaps.
+        // (The groups a list starts from are those of every Set of its window: a superset of the
+        // Sets before the Swap, and a group without a log raises nothing.)
+        if (any_swap) {
+            std::vector<uint64_t> extra;
+            std::vector<uint32_t> cellset;
+            for (const auto& kv : w->rq_index) {
+                const int32_t sl = w->slot_of_obj[kv.first >> 3];
+                if (sl < 0) continue;
+                bool sw = false;
+                for (uint32_t i : kv.second) sw = sw || w->rsq[i].op == 4;
+                if (!sw) continue;
+                const uint32_t rec = (uint32_t)(kv.first & 7);
+                const int cols = w->tab.rec_cols[rec];
+                cellset.clear();  // row << 8 | col, sorted
+                for (uint32_t i : kv.second)
+                    if (w->rsq[i].op == 0) cellset.push_back(w->rsq[i].rrc & 0xFFFF);
+                std::sort(cellset.begin(), cellset.end());
+                cellset.erase(std::unique(cellset.begin(), cellset.end()), cellset.end());
+                auto has = [&](uint32_t key) { return std::binary_search(cellset.begin(), cellset.end(), key); };
+                auto add = [&](uint32_t key) {
+                    cellset.insert(std::lower_bound(cellset.begin(), cellset.end(), key), key);
+                    extra.push_back(((uint64_t)(uint32_t)sl << 19) | (rec << 16) | key);
+                };
+                for (uint32_t i : kv.second) {
+                    if (w->rsq[i].op != 4) continue;
+                    const uint32_t a = (w->rsq[i].rrc >> 8) & 0xFF, b = w->rsq[i].rrc & 0xFF;
+                    for (uint32_t c = 0; a != b && c < (uint32_t)cols; c++) {
+                        const bool ha = has((a << 8) | c), hb = has((b << 8) | c);
+                        if (ha && !hb) add((b << 8) | c);
+                        if (hb && !ha) add((a << 8) | c);
+                    }
+                }
+            }
+            if (!extra.empty()) {
+                std::sort(extra.begin(), extra.end());
+                std::vector<uint32_t> s2, r2, f2;
+                const size_t ng0 = rs_slot.size();
+                for (size_t gi = 0, xi = 0; gi < ng0 || xi < extra.size();) {
+                    const uint64_t kg = gi < ng0 ? ((uint64_t)rs_slot[gi] << 19) | (rs_rrc[gi] & 0x7FFFF) : ~0ull;
+                    const uint64_t kx = xi < extra.size() ? extra[xi] : ~0ull;
+                    if (kx < kg) {
+                        s2.push_back((uint32_t)(kx >> 19));
+                        r2.push_back((uint32_t)(kx & 0x7FFFF) | 0x80000000u);
+                        f2.push_back(gi < ng0 ? rs_first[gi] : (uint32_t)k);
+                        xi++;
+                    } else {
+                        s2.push_back(rs_slot[gi]);
+                        r2.push_back(rs_rrc[gi]);
+                        f2.push_back(rs_first[gi]);
+                        gi++;
+                    }
+                }
+                rs_slot.swap(s2);
+                rs_rrc.swap(r2);
+                rs_first.swap(f2);
+            }
+        }
         rs_first.push_back((uint32_t)k);
+        // the group of (slot, rec << 16 | row << 8 | col), or -1
+        auto group_of = [&](uint32_t sl, uint32_t rrc) -> int64_t {
+            const uint64_t key = ((uint64_t)sl << 19) | (rrc & 0x7FFFF);
+            size_t lo = 0, hi = rs_slot.size();
+            while (lo < hi) {
+                const size_t m = (lo + hi) / 2;
+                const uint64_t km = ((uint64_t)rs_slot[m] << 19) | (rs_rrc[m] & 0x7FFFF);
+                if (km < key) lo = m + 1;
+                else hi = m;
+            }
+            return lo < rs_slot.size() && (((uint64_t)rs_slot[lo] << 19) | (rs_rrc[lo] & 0x7FFFF)) == key ? (int64_t)lo : -1;
+        };
         // the row-operation lists (one per pair, pair order), their calls in call order
         const size_t npair = rowpairs.size();
         if (npair) {
@@ -4186,15 +4335,19 @@ static int execute_frame(World* w, int64_t now_ms, bool calls_only) {
                 rc_bits[at] = x.bits;
                 if (w->rec_obj) rc_bits_h[at] = w->rsq_head(i);
                 if (x.op == 0) {  // its cell's group (binary search over the sorted groups)
-                    const uint64_t key = ((uint64_t)(rowpairs[q] >> 3) << 19) | (x.rrc & 0x7FFFF);
-                    size_t lo = 0, hi = rs_slot.size();
-                    while (lo < hi) {
-                        const size_t m = (lo + hi) / 2;
-                        const uint64_t km = ((uint64_t)rs_slot[m] << 19) | (rs_rrc[m] & 0x7FFFF);
-                        if (km < key) lo = m + 1;
-                        else hi = m;
+                    rc_aux[at] = (uint32_t)group_of((uint32_t)(rowpairs[q] >> 3), x.rrc);
+                } else if (x.op == 4) {  // the columns in which both rows have a group: their logs change places
+                    rc_aux[at] = (uint32_t)(rs_swap.size() / 2);
+                    const uint32_t sl = (uint32_t)(rowpairs[q] >> 3);
+                    for (uint32_t c = 0; row != col && c < (uint32_t)w->tab.rec_cols[rec]; c++) {
+                        const int64_t ga = group_of(sl, (rec << 16) | (row << 8) | c);
+                        const int64_t gb = group_of(sl, (rec << 16) | (col << 8) | c);
+                        if (ga < 0 || gb < 0) continue;
+                        rs_swap.push_back((uint32_t)ga);
+                        rs_swap.push_back((uint32_t)gb);
                     }
-                    rc_aux[at] = (uint32_t)lo;
+                    rc_bits[at] = rs_swap.size() / 2 - rc_aux[at];
+                    evb[q] += 1u;
                 } else {
                     rc_aux[at] = x.aux;
                     evb[q] += x.op == 3 ? (uint32_t)w->tab.rec_rows[rec] : 1u;
@@ -4294,7 +4447,8 @@ static int execute_frame(World* w, int64_t now_ms, bool calls_only) {
     // the SetRecordObject calls' head halves, beside rs_bits and rc_bits (a world with an object column)
     const bool robj = w->rec_obj;
     size_t off_rbh = align16(off_rv + (nrl ? nval * 8 : 0)), off_cbh = align16(off_rbh + (robj ? nrc * 8 : 0));
-    size_t total = align16(off_cbh + (robj ? nrcall * 8 : 0));
+    const size_t off_sw = align16(off_cbh + (robj ? nrcall * 8 : 0));  // the Swaps' group pairs
+    size_t total = align16(off_sw + rs_swap.size() * 4);
     // device fold scratch: keys, sorted keys, call indices, sorted indices, group starts [ng + 1],
     // the groups (slot, property, first call [ng + 1]), the sorted values (and head halves), then
     // the radix sort's temporary storage
@@ -4388,6 +4542,7 @@ static int execute_frame(World* w, int64_t now_ms, bool calls_only) {
             memcpy(P + off_cb, rc_bits.data(), nrcall * 8);
             if (robj) memcpy(P + off_cbh, rc_bits_h.data(), nrcall * 8);
             if (nval) memcpy(P + off_rv, w->rvals.data(), nval * 8);
+            if (!rs_swap.empty()) memcpy(P + off_sw, rs_swap.data(), rs_swap.size() * 4);
         }
         HIPCHK(hipMemcpyAsync(w->stage, w->pin, total, hipMemcpyHostToDevice, w->stream));
         HIPCHK(hipEventRecord(w->pin_done, w->stream));
@@ -4424,6 +4579,7 @@ static int execute_frame(World* w, int64_t now_ms, bool calls_only) {
     rh.rs_old_h = nrss && robj ? (uint64_t*)w->rs_buf + 2 * ngr : nullptr;
     rh.rs_new_h = nrss && robj ? (uint64_t*)w->rs_buf + 3 * ngr : nullptr;
     rh.rc_bits_h = nrl && robj ? (const uint64_t*)(S + off_cbh) : nullptr;
+    rh.rs_swap = rs_swap.empty() ? nullptr : (const uint32_t*)(S + off_sw);
     rh.re_old_h = w->re_old_h;
     rh.re_new_h = w->re_new_h;
     d.rss_ev = nrss ? (uint32_t*)w->rss_buf : nullptr;
@@ -5179,10 +5335,9 @@ int nfk_read_events(void* world, int32_t* ev_obj, int32_t* ev_pid, uint64_t* ev_
     return NFK_OK;
 }
 
-// whether a record event word (op << 24 | rec << 16 | row << 8 | col below the slot field) is the
-// Update of an object cell: the events whose head halves the device writes
+// whether a record event word in the host format (op << 24 | rec << 16 | row << 8 | col; rrc_host
+// of a raw word) is the Update of an object cell: the events whose head halves the device writes
 static bool rrc_obj_update(const World* w, uint32_t rrc) {
-    rrc &= kRrcHost;
     return (rrc >> 24) == 0 && w->rec_ctype[(rrc >> 16) & 0xFF][rrc & 0xFF] == NFK_REC_OBJ_DATA;
 }
 
@@ -5227,7 +5382,7 @@ int nfk_read_rec_events(void* world, int32_t* re_obj, uint32_t* re_rrc, uint64_t
     for (int t = 0; t < d.n_rtiles; t++)
         for (uint32_t i = rb[(size_t)t]; i < rb[(size_t)t + 1] && i < n; i++) {
             re_obj[i] = w->obj_of_slot[(size_t)t * kRTile + (re_rrc[i] >> kRrcSitShift)];
-            re_rrc[i] &= kRrcHost;
+            re_rrc[i] = rrc_host(re_rrc[i]);
         }
     return NFK_OK;
 }
@@ -5251,7 +5406,7 @@ int nfk_read_rec_events_obj(void* world, uint64_t* re_old_h, uint64_t* re_new_h)
     GATHER(w, w->re_old_h, d.re_base, d.n_rtiles, d.re_tcap, n, re_old_h);
     GATHER(w, w->re_new_h, d.re_base, d.n_rtiles, d.re_tcap, n, re_new_h);
     for (size_t i = 0; i < n; i++)  // (unwritten but for the Updates of object cells)
-        if (!rrc_obj_update(w, rrc[i])) re_old_h[i] = re_new_h[i] = 0;
+        if (!rrc_obj_update(w, rrc_host(rrc[i]))) re_old_h[i] = re_new_h[i] = 0;
     return NFK_OK;
 }
 

@@ -888,6 +888,9 @@ struct RecHeads {
     uint64_t* rs_new_h;
     uint64_t* re_old_h;
     uint64_t* re_new_h;
+    // SwapRowInfo: [][2] the groups of (origin, col) and (target, col) whose logs a Swap exchanges,
+    // one pair per column with a group; a call's pairs at rc_aux[k], (uint32_t)rc_bits[k] of them
+    const uint32_t* rs_swap;
 };
 
 __global__ __launch_bounds__(kTPB) void k_rsets(Dev d, RecHeads h) {
@@ -969,7 +972,10 @@ __global__ __launch_bounds__(kTPB) void k_rsets(Dev d, RecHeads h) {
 //   AddRow(row, values) (RC:111-180): row -1 takes the first unused row (none: nothing); a used
 //       row is covered; the cells are written without Update events; one Add / Cover event;
 //   Remove(row) (RC:1086-1107): a used row's Del event, then the row is unused (cells kept);
-//   ClearRecord (KM:492 -> RC:1109): Remove from the last row to the first.
+//   ClearRecord (KM:492 -> RC:1109): Remove from the last row to the first;
+//   SwapRowInfo(origin, target) (RC:1219-1253): nothing on an unused origin; else every physical
+//       column's cells and the two used bits are exchanged, and with them the two rows' groups (has,
+//       old, new and the head halves: the window's Update log follows the row); one Swap event.
 // one slot's record vectors [cols][rows] moved from the places of mask `from` to those of `to`
 __device__ void rec_repack(uint64_t* cells, int rows, int cols, uint64_t rowm, uint64_t from, uint64_t to) {
     if (from == to) return;
@@ -1060,6 +1066,40 @@ __global__ __launch_bounds__(kTPB) void k_rrows(Dev d, RecHeads h) {
             if (!((used >> row) & 1)) continue;
             ev[nev++] = (2u << 8) | row;
             used &= ~(1ull << row);
+        } else if (op == 4) {
+            const uint32_t tgt = col;  // (the col field carries the target row)
+            if (!((used >> row) & 1)) continue;  // RC:1221
+            ev[nev++] = (4u << 8) | row | (tgt << 16);
+            if (tgt == row) continue;
+            for (int c = 0; c < cols; c++) {
+                uint64_t* v = cells + (size_t)c * rows;
+                const uint64_t t = v[row];
+                v[row] = v[tgt];
+                v[tgt] = t;
+            }
+            const uint64_t ub = (used >> tgt) & 1;  // (the origin's bit is set)
+            used = (used & ~(1ull << row)) | (ub << row) | (1ull << tgt);
+            const uint32_t* sp = h.rs_swap + 2 * (size_t)d.rc_aux[k];
+            for (uint32_t q = 0, nq = (uint32_t)d.rc_bits[k]; q < nq; q++) {
+                const uint32_t ga = sp[2 * q], gb = sp[2 * q + 1];
+                const uint8_t th = d.rs_has[ga];
+                d.rs_has[ga] = d.rs_has[gb];
+                d.rs_has[gb] = th;
+                uint64_t t = d.rs_old[ga];
+                d.rs_old[ga] = d.rs_old[gb];
+                d.rs_old[gb] = t;
+                t = d.rs_new[ga];
+                d.rs_new[ga] = d.rs_new[gb];
+                d.rs_new[gb] = t;
+                if (h.rs_old_h) {
+                    t = h.rs_old_h[ga];
+                    h.rs_old_h[ga] = h.rs_old_h[gb];
+                    h.rs_old_h[gb] = t;
+                    t = h.rs_new_h[ga];
+                    h.rs_new_h[ga] = h.rs_new_h[gb];
+                    h.rs_new_h[gb] = t;
+                }
+            }
         } else {
             for (int q = rows - 1; q >= 0; q--)
                 if ((used >> q) & 1) {
@@ -1138,7 +1178,7 @@ __global__ __launch_bounds__(kTPB) void k_rset_slots(Dev d, RecHeads h) {
                 bytes += 4 * (per + np);
             }
         };
-        // the record's row events first (AddRow / Remove / Clear, in call order: k_rrows)
+        // the record's row events first (AddRow / Remove / Clear / Swap, in call order: k_rrows)
         if (li < d.n_rl && d.rl_slot[li] == (uint32_t)e && d.rl_rec[li] == (uint32_t)r) {
             const unsigned nrow = d.rl_cnt[li];
             if constexpr (kEmit) {
@@ -1147,7 +1187,10 @@ __global__ __launch_bounds__(kTPB) void k_rset_slots(Dev d, RecHeads h) {
                     const uint32_t x = rev[q];
                     const unsigned at = pos + q;
                     const uint32_t lmo = pmsg + per * q;
-                    d.re_rrc[re0 + at] = sit | ((x >> 8) << 24) | ((uint32_t)r << 16) | ((x & 0xFF) << 8);
+                    // (a Swap: kRrcSwap with op bits 0, the origin in the row field, the target in the col field)
+                    d.re_rrc[re0 + at] = ((x >> 8) & 0xFF) == 4u
+                                             ? sit | kRrcSwap | ((uint32_t)r << 16) | ((x & 0xFF) << 8) | (x >> 16)
+                                             : sit | ((x >> 8) << 24) | ((uint32_t)r << 16) | ((x & 0xFF) << 8);
                     d.re_old[re0 + at] = 0;
                     d.re_new[re0 + at] = 0;
                     if (!d.fuse_rec) d.re_moff[re0 + at] = lmo;  // (fused: the readers count, k_counted_moff)
@@ -1729,7 +1772,7 @@ __global__ __launch_bounds__(kTPB) void k_fanout(Dev d, int32_t blk0) {
         if (i < tcap) {
             const uint32_t x = slots[off0 + i];
             slot[q] = rec ? s_base + (x >> kRrcSitShift) : x;
-            key[q] = rec ? ((x >> 16) & 0xFF) : d.ev_pid[off0 + i];
+            key[q] = rec ? ((x >> 16) & 7u) : d.ev_pid[off0 + i];  // (a record index: kRrcSwap sits above)
             lm[q] = moff[off0 + i];
         }
     }
@@ -1755,7 +1798,7 @@ __global__ __launch_bounds__(kTPB) void k_fanout(Dev d, int32_t blk0) {
                 if (i < cnt) {
                     const uint32_t x = slots[off0 + i];
                     slot[q] = rec ? s_base + (x >> kRrcSitShift) : x;
-                    key[q] = rec ? ((x >> 16) & 0xFF) : d.ev_pid[off0 + i];
+                    key[q] = rec ? ((x >> 16) & 7u) : d.ev_pid[off0 + i];  // (a record index: kRrcSwap sits above)
                     lm[q] = moff[off0 + i];
                 }
             }
@@ -2192,7 +2235,7 @@ __global__ __launch_bounds__(kTPB) void k_compact_rec(const uint32_t* __restrict
         for (uint32_t i = threadIdx.x; i < n; i += kTPB) {
             const uint32_t x = src[(size_t)t * tcap + i];
             obj[b + i] = slot_obj[(uint32_t)t * (uint32_t)kRTile + (x >> kRrcSitShift)];
-            rrc[b + i] = x & kRrcHost;
+            rrc[b + i] = rrc_host(x);
         }
     }
 }
@@ -2224,7 +2267,7 @@ __global__ __launch_bounds__(kTPB) void k_counted_moff(Dev d, int rec, uint32_t*
                 if (rec) {
                     const uint32_t x = d.re_rrc[(size_t)t * tcap + i];
                     slot = (uint32_t)t * (uint32_t)kRTile + (x >> kRrcSitShift);
-                    key = (x >> 16) & 0xFF;
+                    key = (x >> 16) & 7u;  // (bits 16-18: kRrcSwap sits above)
                 } else {
                     slot = d.ev_slot[(size_t)t * tcap + i];
                     key = d.ev_pid[(size_t)t * tcap + i];

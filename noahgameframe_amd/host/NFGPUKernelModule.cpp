@@ -938,6 +938,26 @@ bool NFGPUKernelModule::RemoveRow(const NFGUID& self, const std::string& strReco
     return true;
 }
 
+// NFCRecord::SwapRowInfo (RC:1219-1253): the reference's return value, from the used-row mask as the
+// reference holds it now (the window's queued calls replayed)
+bool NFGPUKernelModule::SwapRowInfo(const NFGUID& self, const std::string& strRecordName, int nOriginRow,
+                                    int nTargetRow) {
+    using Fn = int (*)(void*, int32_t, const int64_t*, const int64_t*, const int32_t*, const int32_t*, const int32_t*);
+    static const Fn fn = (Fn)nfgpu_symbol("nfk_swap_rows");  // (looked up at first use, as nfk_query_objects)
+    if (!fn) throw std::runtime_error("nfk_swap_rows: the nfgpu library has no such entry point");
+    Flush();  // (the buffered Set calls first: call order)
+    auto it = record_id_.find(strRecordName);
+    if (!committed_ || it == record_id_.end() || ObjectIndex(self) < 0) return false;
+    const int rows = records_[it->second].rows;
+    if (nOriginRow < 0 || nOriginRow >= rows || nTargetRow < 0 || nTargetRow >= rows) return false;
+    if (!((UsedRows(self, it->second) >> nOriginRow) & 1)) return false;  // RC:1221
+    const int32_t rec = it->second, ro = nOriginRow, rt = nTargetRow;
+    if (fn(world_, 1, &self.nHead64, &self.nData64, &rec, &ro, &rt) != NFK_OK) return false;
+    if (shard_) NoteCall(self);
+    pending_calls_++;
+    return true;
+}
+
 // NFCKernelModule::ClearRecord (KM:492) -> NFCRecord::Clear (RC:1109)
 bool NFGPUKernelModule::ClearRecord(const NFGUID& self, const std::string& strRecordName) {
     Flush();  // (the buffered Set calls first: call order)
@@ -1820,13 +1840,15 @@ void NFGPUKernelModule::DeliverEvents(const nfk_frame_host& f, const NFGUID* ev_
     int ev_r = -1;  // the record ev.strRecordName holds (a name copy per event would allocate)
     for (int64_t e = 0; e < f.n_re; e++) {
         const uint32_t rrc = f.re_rrc[e];
-        const int r = (rrc >> 16) & 0xFF, row = (rrc >> 8) & 0xFF, col = rrc & 0xFF, op = (rrc >> 24) & 3;
-        // row events (AddRow / Remove / Clear) carry empty values, as NFCRecord raises them (RC:177, 1098)
+        const int r = (rrc >> 16) & 0xFF, row = (rrc >> 8) & 0xFF, col = rrc & 0xFF, op = (rrc >> 24) & 7;
+        // row events (AddRow / Remove / Clear / Swap) carry empty values, as NFCRecord raises them
+        // (RC:177, 1098, 1246)
         ev.nOpType = op == 1 ? RECORD_EVENT_DATA::Add : op == 2 ? RECORD_EVENT_DATA::Del
-                   : op == 3 ? RECORD_EVENT_DATA::Cover : RECORD_EVENT_DATA::Update;
-        // the event names the physical column (an object cell: its data half); callbacks get the logical one
+                   : op == 3 ? RECORD_EVENT_DATA::Cover : op == 4 ? RECORD_EVENT_DATA::Swap : RECORD_EVENT_DATA::Update;
+        // the event names the physical column (an object cell: its data half); callbacks get the logical
+        // one; a Swap's col field is its target ROW (RC:1243) and is handed on as it is
         const RecordDef& rd = records_[r];
-        const int lcol = op ? 0 : rd.logical[(size_t)col];
+        const int lcol = op == 4 ? col : op ? 0 : rd.logical[(size_t)col];
         ev.nRow = row;
         ev.nCol = lcol;
         if (r != ev_r) {

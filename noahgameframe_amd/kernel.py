@@ -151,6 +151,7 @@ def load_library(path=LIB_PATH):
         "nfk_get_record_objects": [VP, I32, VP, VP, VP, VP, VP, VP, VP],
         "nfk_find_objects": [VP, I32, VP, VP, VP, VP, VP, VP, VP],
         "nfk_find_objects_obj": [VP, I32, VP, VP, VP, VP, VP, VP], "nfk_read_rec_events_obj": [VP, VP, VP],
+        "nfk_swap_rows": [VP, I32, VP, VP, VP, VP, VP],
     }
     for name, args in sig.items():
         if not hasattr(lib, name) and os.environ.get("NFGPU_LIB"):
@@ -322,6 +323,33 @@ class NFKernelModule:
 
     def ClearRecord(self, guid, rec):
         self.record_rows([guid[0]], [guid[1]], [rec], [3], [0])
+        return True
+
+    # ---- NFCRecord::SwapRowInfo (RC:1219-1253) ----
+    def swap_rows(self, guid_head, guid_data, rec, origin, target):
+        """nfk_swap_rows: queued in call order with set_records / set_record_objects / record_rows;
+        a used origin row changes places with the target row (cells of every column, used bits, the
+        window's Update log) and raises one Swap event, rrc = 4 << 24 | rec << 16 | origin << 8 | target"""
+        a = [np.ascontiguousarray(x, t) for x, t in
+             ((guid_head, np.int64), (guid_data, np.int64), (rec, np.int32), (origin, np.int32), (target, np.int32))]
+        self._chk(self.lib.nfk_swap_rows(self.h, len(a[0]), *[_p(x) for x in a]))
+
+    def get_used_rows(self, guid_head, guid_data, rec):
+        """nfk_get_used_rows -> uint64 used-row masks, this window's queued row calls replayed"""
+        a = [np.ascontiguousarray(x, t) for x, t in ((guid_head, np.int64), (guid_data, np.int64), (rec, np.int32))]
+        out = np.zeros(len(a[0]), np.uint64)
+        self._chk(self.lib.nfk_get_used_rows(self.h, len(a[0]), *[_p(x) for x in a], _p(out)))
+        return out
+
+    def SwapRowInfo(self, guid, rec, origin, target):
+        """NFCRecord::SwapRowInfo: False (nothing queued) for an unknown record, a row outside the
+        record or an origin that is unused now (the window's queued calls replayed); else queued"""
+        shape = self.rec_shape.get(rec)
+        if shape is None or origin < 0 or origin >= shape[1] or target < 0 or target >= shape[1]:
+            return False
+        if not (int(self.get_used_rows([guid[0]], [guid[1]], [rec])[0]) >> origin) & 1:
+            return False
+        self.swap_rows([guid[0]], [guid[1]], [rec], [origin], [target])
         return True
 
     # ---- NFIKernelModule::SetRecordObject / NFCRecord::GetObject (RC:367-421 / RC:697-716) ----
