@@ -147,6 +147,36 @@ __host__ __device__ __forceinline__ int64_t riadd_clamp(int64_t cur, int64_t a, 
     return r > hi ? hi : r;
 }
 static_assert(kMaxW == NFK_MAX_TOUCH, "writable slots = touch capacity");
+// NaN results of the f64 ops as the reference's x86-64 code makes them.  The values are the same IEEE
+// doubles everywhere, but which NaN an operation returns is the machine's: an SSE2 add / sub / mul returns
+// its first source operand when that is a NaN, else its second (quieted, sign kept), and the "real
+// indefinite" 0xFFF8000000000000 (sign set) for an invalid operation such as inf - inf or inf * 0; this GPU
+// returns 0x7FF8000000000000 for the latter, and its compiler turns `t - x` into `t + -x` on a negated
+// operand, which flips a NaN x's sign — in one build of the same source and not in another.  NaNs are
+// rare, so the ops compute r plainly and come here only when r is a NaN (a NaN in any step ends in one).
+// nan_of: r = a op b, operands in the order the reference's compiled code has them.
+__host__ __device__ __forceinline__ double nan_of(double r, double a, double b) {
+    if (r == r) return r;
+    unsigned long long u;
+    if (a != a) __builtin_memcpy(&u, &a, 8);
+    else if (b != b) __builtin_memcpy(&u, &b, 8);
+    else u = 0xFFF0000000000000ull;
+    u |= 0x0008000000000000ull;
+    double q;
+    __builtin_memcpy(&q, &u, 8);
+    return q;
+}
+// FLERP's x + (tg - x) * k (the add keeps m's NaN before x's: the reference's `x + m` compiles to an add
+// whose first source is m) and FAFFINE's / RFAFFINE's x * a + b, when the plain result is a NaN
+__host__ __device__ __forceinline__ double flerp_nan(double x, double tg, double k) {
+    const double dd = nan_of(tg - x, tg, x);
+    const double m = nan_of(dd * k, dd, k);
+    return nan_of(x + m, m, x);
+}
+__host__ __device__ __forceinline__ double faffine_nan(double x, double a, double b) {
+    const double m = nan_of(x * a, x, a);
+    return nan_of(m + b, m, b);
+}
 
 // record op as k_records sees it (Dev::rops, kernel-argument space, so every field is a scalar):
 // cells/used of its record, its shape, and the [gfirst, glast] span of ops on the same record

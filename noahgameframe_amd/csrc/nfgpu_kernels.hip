@@ -566,9 +566,11 @@ __device__ __forceinline__ void run_program_chunk(Ent& en, const Tables* __restr
                 const double dd = tg - x;
                 const double m = dd * __longlong_as_double(op.b);
                 v = x + m;
+                if (v != v) v = flerp_nan(x, tg, __longlong_as_double(op.b));
             } else {
                 const double m = x * __longlong_as_double(op.a);
                 v = m + __longlong_as_double(op.b);
+                if (v != v) v = faffine_nan(x, __longlong_as_double(op.a), __longlong_as_double(op.b));
             }
             if (!(fabs(v - x) <= 1e-15)) {  // NFCProperty::SetFloat (PR:314): IsZeroDouble(v - cur)
                 en.tput(op.dst, (uint64_t)__double_as_longlong(x), (uint64_t)__double_as_longlong(v));
@@ -1256,7 +1258,8 @@ __global__ __launch_bounds__(kTPB) void k_rset_slots(Dev d, RecHeads h) {
                 } else {
                     const double x = __longlong_as_double((long long)cur);
                     const double m = x * __longlong_as_double(oa);
-                    const double v = m + __longlong_as_double(obb);
+                    double v = m + __longlong_as_double(obb);
+                    if (v != v) v = faffine_nan(x, __longlong_as_double(oa), __longlong_as_double(obb));
                     const double df = v - x;
                     if (!(df < 0.001 && df > -0.001)) {  // NFIDataList.h:106-113
                         nb = (uint64_t)__double_as_longlong(v);
@@ -1492,7 +1495,8 @@ __global__ __launch_bounds__(kTPB) void k_records(Dev d) {
                 } else {
                     const double x = __longlong_as_double((long long)c);
                     const double m = x * __longlong_as_double((long long)op_a[j]);
-                    const double v = m + __longlong_as_double((long long)op_b[j]);
+                    double v = m + __longlong_as_double((long long)op_b[j]);
+                    if (v != v) v = faffine_nan(x, __longlong_as_double((long long)op_a[j]), __longlong_as_double((long long)op_b[j]));
                     const double df = v - x;
                     changed = !(df < 0.001 && df > -0.001);  // NFIDataList.h:106-113
                     nb = (uint64_t)__double_as_longlong(v);

@@ -111,9 +111,11 @@ __device__ __forceinline__ void run_programs_u(uint64_t (&v)[kU], uint32_t& wm, 
                     const double dd = tg - x;
                     const double m = dd * __longlong_as_double(tab->opx[k][i].b);
                     r = x + m;
+                    if (r != r) r = flerp_nan(x, tg, __longlong_as_double(tab->opx[k][i].b));
                 } else {
                     const double m = x * __longlong_as_double(tab->opx[k][i].a);
                     r = m + __longlong_as_double(tab->opx[k][i].b);
+                    if (r != r) r = faffine_nan(x, __longlong_as_double(tab->opx[k][i].a), __longlong_as_double(tab->opx[k][i].b));
                 }
                 const bool set = !(fabs(r - x) <= 1e-15);  // NFCProperty::SetFloat (PR:314): IsZeroDouble(v - cur)
                 uput(v, u0, set ? (uint64_t)__double_as_longlong(r) : xb);

@@ -33,6 +33,19 @@ def test_golden_fixtures_are_nontrivial():
     assert n_ev > 1000 and n_msg > 1000 and n_fi > 1000
     r = nfio.read(os.path.join(GOLDEN, "records.expected.nfio"))
     assert sum(len(v) for k, v in r.items() if k.startswith("re_") and k.endswith("_obj")) > 100
+    # arith (tests/golden/gen_arith_golden.py): the reference's own events carry NaNs, infinities, -0.0 and
+    # denormals, and int64 values outside int32
+    a = nfio.read(os.path.join(GOLDEN, "arith.expected.nfio"))
+    assert "arith" in [os.path.basename(p)[:-len(".workload.nfio")] for p in glob.glob(os.path.join(GOLDEN, "*.workload.nfio"))]
+    w = nfio.read(os.path.join(GOLDEN, "arith.workload.nfio"))
+    n_int = int(w["cfg"][1])
+    pid = np.concatenate([v for k, v in sorted(a.items()) if k.startswith("ev_") and k.endswith("_pid")])
+    new = np.concatenate([v for k, v in sorted(a.items()) if k.startswith("ev_") and k.endswith("_new")])
+    assert len(pid) > 1000
+    f, i = new[pid >= n_int].view(np.float64), new[pid < n_int].view(np.int64)
+    assert np.isnan(f).sum() > 20 and np.isinf(f).sum() > 20 and ((f == 0) & np.signbit(f)).sum() > 5
+    assert ((f != 0) & (np.abs(f) < np.finfo(np.float64).tiny)).sum() > 5
+    assert ((i > 2 ** 31) | (i < -2 ** 31)).sum() > 100
 
 
 @pytest.mark.skipif(not have_ref, reason="oracle/_ref not built (needs /root/reference)")
