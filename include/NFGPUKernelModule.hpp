@@ -392,6 +392,9 @@ public:
     // events are delivered before Execute returns (nfk_execute_calls).  Off: they land in the
     // next frame.  Default on.
     void SetFunctorCallsSameFrame(bool on) { same_frame_ = on; }
+    // nfk_config.slack_per_256 of the world AfterInit creates: the free slots kept per 256 members of a
+    // scene group for arrivals (0: the library's default, -1: none).  Before AfterInit.
+    void SetSlackPer256(int n) { slack_per_256_ = n; }
     int64_t Now() const { return clock_(); }
 
     // ---- NFIKernelModule ----
@@ -685,6 +688,7 @@ private:
     int64_t pending_calls_ = 0;  // calls queued since the last device pass
     void* world_ = nullptr;
     int capacity_;
+    int slack_per_256_ = 0;
     void* stream_;
     bool committed_ = false;
     std::vector<PropertyDef> props_;

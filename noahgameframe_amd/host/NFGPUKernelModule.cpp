@@ -276,6 +276,7 @@ bool NFGPUKernelModule::AfterInit() {
     cfg.n_kind = (int)heartbeats_.size();
     cfg.n_rec = (int)records_.size();
     cfg.stream = stream_;
+    cfg.slack_per_256 = slack_per_256_;
     check(nfk_create(&cfg, &world_), "nfk_create");
     const int np = n_int + n_flt + n_obj;
     for (int c = 0; c < (int)classes_.size(); c++) {

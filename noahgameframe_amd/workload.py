@@ -667,11 +667,12 @@ def _lifecycle_world(kw):
     bt = born[s_late["s_obj"]]
     order = np.argsort(bt, kind="stable")
     tt = w["tick_time"]
+    st_late = s_late["s_time"][order]
+    st_min = st_late.min() if len(st_late) else 0   # (a destroy-only world has no late objects)
     h_new = dict(h_tick=bt[order], h_op=np.ones(len(order), np.int32), h_obj=s_late["s_obj"][order],
                  h_kind=s_late["s_kind"][order], h_interval=s_late["s_interval"][order],
                  h_count=s_late["s_count"][order],
-                 h_time=(tt[np.maximum(bt[order] - 1, 0)] + (s_late["s_time"][order] - s_late["s_time"][order].min()) % 100
-                         ).astype(np.int64))
+                 h_time=(tt[np.maximum(bt[order] - 1, 0)] + (st_late - st_min) % 100).astype(np.int64))
     # the window's schedule calls: the creations' AddSchedule first, then the generator's
     ht = np.concatenate([h_new["h_tick"], w["h_tick"]])
     first = np.concatenate([np.zeros(len(order), np.int8), np.ones(len(w["h_tick"]), np.int8)])

@@ -5,8 +5,9 @@
 // Execute —
 // and records what the callbacks receive, in the oracle's output layout.
 //
-// usage: plugin_replay <workload.nfio> <out.nfio>
+// usage: plugin_replay <workload.nfio> <out.nfio> [slack_per_256]
 #include <cstdio>
+#include <cstdlib>
 #include <cstring>
 #include <string>
 #include <vector>
@@ -22,7 +23,7 @@ static int64_t g_now = 0;
 static std::string cstr(const uint8_t* p) { return std::string((const char*)p, strnlen((const char*)p, 32)); }
 
 int main(int argc, char** argv) {
-    if (argc != 3) return 2;
+    if (argc != 3 && argc != 4) return 2;
     nfio_file wf;
     if (nfio_read(argv[1], &wf)) return 2;
     auto A = [&](const char* n) {
@@ -42,6 +43,7 @@ int main(int argc, char** argv) {
 
     NFGPUKernelModule km((int)N);
     km.SetTimeSource([] { return g_now; });
+    if (argc == 4) km.SetSlackPer256(atoi(argv[3]));
     std::vector<std::string> pname(NP), kname(NK), cname = {"NPC", "Player"};
     for (int p = 0; p < NP; p++) {
         pname[p] = cstr(pnames + 32 * p);
@@ -102,18 +104,20 @@ int main(int argc, char** argv) {
     const int64_t ND = dta ? (int64_t)dta->shape[0] : 0;
     int32_t* d_tick = ND ? (int32_t*)dta->data : nullptr;
     int32_t* d_obj = ND ? (int32_t*)A("d_obj")->data : nullptr;
-    km.AfterInit();
-    for (int r = 0; r < NR; r++) {  // record contents: creation-time rows through the C-ABI
+    for (int r = 0; r < NR; r++) {  // creation-time record contents (cells [cols][rows], the used-row mask)
         char nm[32];
         snprintf(nm, sizeof nm, "rec%d_cells", r);
-        nfio_arr* c = A(nm);
+        const uint64_t* c = (const uint64_t*)A(nm)->data;
         snprintf(nm, sizeof nm, "rec%d_used", r);
-        nfio_arr* u = A(nm);
-        (void)c;
-        (void)u;
-        fprintf(stderr, "plugin_replay: records are not replayed through the plugin API yet\n");
-        return 4;
+        const uint64_t* u = (const uint64_t*)A(nm)->data;
+        const size_t per = (size_t)((int32_t*)A("rec_rows")->data)[r] * (size_t)((int32_t*)A("rec_cols")->data)[r];
+        for (int64_t o = 0; o < N; o++)
+            if ((!born || born[o] < 0) &&
+                !km.SetCreationRecord(NFGUID(gh[o], gd[o]), "rec" + std::to_string(r), u[o],
+                                      std::vector<uint64_t>(c + (size_t)o * per, c + (size_t)(o + 1) * per)))
+                return 4;
     }
+    km.AfterInit();
 
     // what the callbacks observe this frame
     std::vector<int32_t> ev_obj, ev_pid, re_obj, fi_obj, fi_kind, fi_rem, mr;
@@ -140,7 +144,10 @@ int main(int argc, char** argv) {
     km.RegisterCommonRecordEvent([&](const NFGUID& self, const RECORD_EVENT_DATA& ev, const TData& a, const TData& b) {
         re_obj.push_back(km.ObjectIndex(self));
         int r = std::stoi(ev.strRecordName.substr(3));
-        re_rrc.push_back(((uint32_t)r << 16) | ((uint32_t)ev.nRow << 8) | (uint32_t)ev.nCol);
+        // (a row event's word carries its kind as the oracle's does: 1 Add, 2 Del, 3 Cover)
+        const uint32_t op = ev.nOpType == RECORD_EVENT_DATA::Add ? 1 : ev.nOpType == RECORD_EVENT_DATA::Del ? 2
+                          : ev.nOpType == RECORD_EVENT_DATA::Cover ? 3 : 0;
+        re_rrc.push_back((op << 24) | ((uint32_t)r << 16) | ((uint32_t)ev.nRow << 8) | (uint32_t)ev.nCol);
         uint64_t x, y;
         if (a.GetType() == TDATA_INT) { x = (uint64_t)a.GetInt(); y = (uint64_t)b.GetInt(); }
         else { double u = a.GetFloat(), v = b.GetFloat(); memcpy(&x, &u, 8); memcpy(&y, &v, 8); }
@@ -212,6 +219,12 @@ int main(int argc, char** argv) {
     int32_t* r_col = NRS ? (int32_t*)A("r_col")->data : nullptr;
     uint64_t* r_bits = NRS ? (uint64_t*)A("r_bits")->data : nullptr;
     uint8_t* r_ct = NRS ? (uint8_t*)A("rec_ctype")->data : nullptr;
+    // record row calls among them (optional): r_op 1 AddRow (r_row -1: the first unused row; r_vals the
+    // row's values), 2 Remove, 3 ClearRecord
+    nfio_arr* roa = NRS ? nfio_get(&wf, "r_op") : nullptr;
+    uint8_t* r_op = roa ? (uint8_t*)roa->data : nullptr;
+    uint64_t* r_vals = roa ? (uint64_t*)A("r_vals")->data : nullptr;
+    int32_t* r_ncol = NRS ? (int32_t*)A("rec_cols")->data : nullptr;
 
     nfio_writer w;
     if (nfio_wopen(&w, argv[2])) return 2;
@@ -251,6 +264,24 @@ int main(int argc, char** argv) {
         for (; ri < NRS && r_tick[ri] == t; ri++) {  // NFIKernelModule::SetRecordInt / SetRecordFloat (KM:505 / 545)
             NFGUID g(gh[r_obj[ri]], gd[r_obj[ri]]);
             const std::string rn = "rec" + std::to_string(r_rec[ri]);
+            if (r_op && r_op[ri]) {
+                if (r_op[ri] == 1) {
+                    std::vector<TData> vals;
+                    for (int c = 0; c < r_ncol[r_rec[ri]]; c++) {
+                        TData v;
+                        const uint64_t bits = r_vals[ri * NFK_MAX_REC_COLS + c];
+                        if (r_ct[r_rec[ri] * NFK_MAX_REC_COLS + c]) { v.type = TDATA_FLOAT; memcpy(&v.f, &bits, 8); }
+                        else { v.type = TDATA_INT; v.i = (int64_t)bits; }
+                        vals.push_back(v);
+                    }
+                    km.AddRow(g, rn, r_row[ri], vals);
+                } else if (r_op[ri] == 2) {
+                    km.RemoveRow(g, rn, r_row[ri]);
+                } else {
+                    km.ClearRecord(g, rn);
+                }
+                continue;
+            }
             if (r_ct[r_rec[ri] * NFK_MAX_REC_COLS + r_col[ri]]) {
                 double v;
                 memcpy(&v, &r_bits[ri], 8);
