@@ -470,6 +470,10 @@ int nfk_read_object(void* world, int32_t pid, int64_t* head /* [n_objects] */, i
 int nfk_read_record(void* world, int32_t rec, uint64_t* cells /* [n_objects][cols][rows] */);
 /* schedule table in creation order: arrays [n_kind][n_objects] */
 int nfk_read_schedules(void* world, int64_t* next_ms, int32_t* remain, uint8_t* state);
+/* how the device holds each schedule, same shape: 1 = a 16-byte wide record behind its 8-byte scan
+ * word, 0 = the compact word alone (or no schedule).  Both forms read the same through
+ * nfk_read_schedules; the form only tells what the timer scan costs. */
+int nfk_read_schedule_forms(void* world, uint8_t* wide);
 int nfk_read_events(void* world, int32_t* ev_obj, int32_t* ev_pid, uint64_t* ev_old, uint64_t* ev_new);
 /* the head halves of the object-property events, dense like nfk_read_events (0 for other events) */
 int nfk_read_events_obj(void* world, uint64_t* ev_old_h, uint64_t* ev_new_h);

@@ -44,8 +44,20 @@ struct alignas(64) Ctrl {
     unsigned long long bytes_tick, bytes_rec, bytes_fan, pad2;          // accumulated across frames
 };
 
-// Schedule table, one 16-byte hot record per (kind, slot) read every frame by the timer scan,
-// and one 16-byte cold record read only when the heartbeat fires (NFCScheduleElement fields).
+// Schedule table.  The timer scan reads one 8-byte WORD per (kind, slot) every frame (Dev::s_word):
+//   bits 0-3    kSt* flags below: present, forever, fired-once, wide
+//   bits 4-36   next (mnNextTriggerTime) as an unsigned offset in ms from Dev::s_epoch (kScNextBits)
+//   bits 37-63  remain (mnRemainCount), signed (kScRemBits)
+// A word without the wide bit is COMPACT: it is the whole hot record, and its step is the kind's
+// common step Dev::s_step[kind] (a wave-uniform scalar; a kind has one once Dev::s_kvalid names
+// it, and it never changes afterwards).  A word with kStWide carries only the present, forever and
+// wide bits: the record is the 16-byte SchedHot below in Dev::s_wide, read under a branch.  A
+// schedule is compact when its step is the kind's common step and fits 28 bits, its next and
+// remain fit their fields, and it is not a forever schedule whose remain has wrapped to >= 0
+// (sc_encode); anything else is wide.  A fire that takes a compact record out of its fields writes
+// the wide record and sets the wide bit in the same fire; nothing migrates back.
+// One 16-byte cold record per (kind, slot) is read only when a heartbeat fires and the hot record
+// cannot give the next time (NFCScheduleElement fields).
 struct alignas(16) SchedHot {
     int64_t next;    // mnNextTriggerTime
     int32_t remain;  // mnRemainCount
@@ -67,6 +79,42 @@ struct alignas(16) SchedCold {
     int32_t all;     // mnAllCount
     float interval;  // mfIntervalTime
 };
+// The 8-byte schedule word (see above).  Its low three flags are SchedHot::state's.
+constexpr uint64_t kScWide = 8;
+constexpr int kScNextBits = 33, kScRemBits = 27;
+// Dev::s_epoch = the time of the world's first AddSchedule - kScEpochBack: start times up to 12
+// days before it, and negative steps, still give an offset >= 0
+constexpr int64_t kScEpochBack = 1ll << 30;
+__host__ __device__ __forceinline__ int64_t sc_off(uint64_t w) { return (int64_t)((w >> 4) & ((1ull << kScNextBits) - 1)); }
+__host__ __device__ __forceinline__ int32_t sc_remain(uint64_t w) { return (int32_t)((int64_t)w >> (64 - kScRemBits)); }
+__host__ __device__ __forceinline__ bool sc_fits(int64_t off, int32_t remain) {
+    return (uint64_t)off < (1ull << kScNextBits) && remain >= -(1 << (kScRemBits - 1)) && remain < (1 << (kScRemBits - 1));
+}
+__host__ __device__ __forceinline__ uint64_t sc_word(uint32_t flags, int64_t off, int32_t remain) {
+    return (uint64_t)(flags & 7u) | ((uint64_t)off << 4) | ((uint64_t)(int64_t)remain << (64 - kScRemBits));
+}
+// the wide record a compact word stands for (step: its kind's common step)
+__host__ __device__ __forceinline__ SchedHot sc_decode(uint64_t w, int64_t epoch, int32_t step) {
+    SchedHot h;
+    h.next = epoch + sc_off(w);
+    h.remain = sc_remain(w);
+    h.state = ((uint32_t)w & 7u) | st_pack_step(step);
+    return h;
+}
+// the word of a wide record: its flags only (0: no schedule)
+__host__ __device__ __forceinline__ uint64_t sc_wide_word(uint32_t state) {
+    return (state & kStPresent) ? (uint64_t)(state & (kStPresent | kStForever)) | kScWide : 0ull;
+}
+// The compact word of a hot record, or 0 when the record has to be wide (or is absent).  valid:
+// the kind has a common step; step: that step.
+__host__ __device__ __forceinline__ uint64_t sc_encode(const SchedHot& h, int64_t epoch, int32_t step, bool valid) {
+    if (!valid || !(h.state & kStPresent) || !(h.state & kStStep) || st_step(h.state) != (int64_t)step) return 0ull;
+    if ((h.state & kStForever) && h.remain >= 0) return 0ull;  // wrapped through INT32_MIN: reads the cold record
+    if (h.next < epoch) return 0ull;
+    const uint64_t off = (uint64_t)h.next - (uint64_t)epoch;
+    if (off >= (1ull << kScNextBits) || !sc_fits((int64_t)off, h.remain)) return 0ull;
+    return sc_word(h.state, (int64_t)off, h.remain);
+}
 
 // four u32 at a dword-aligned address (gfx950 global memory allows it; one 16-byte store)
 typedef uint32_t u32x4_a4 __attribute__((ext_vector_type(4), aligned(4)));
@@ -91,6 +139,7 @@ constexpr unsigned kAblNoFuse = 4096;  // fan-out in k_fanout instead of k_tick'
 constexpr unsigned kAblFanTriples = 1u << 16;  // k_tick fan-out: short runs through the event triples and window passes for every tile, no direct window
 constexpr unsigned kAblFanWin16 = 1u << 24, kAblFanWin32 = 1u << 25;  // k_tick fan-out LDS window up to 16 / 32 recipients
 constexpr unsigned kAblScanKernel = 1u << 28;  // dense ranks by k_scan_tiles for every world
+constexpr unsigned kAblSchedWide = 1u << 15;  // no kind gets a common step: every schedule record is wide
 // a check, outputs exact: k_tick marks every kind's remain slot (s_rem) unwritten at its start and
 // raises kErrRemain when the fired list reads one for a counted heartbeat that the schedule scan
 // did not write (a counted heartbeat's remain is >= 0 after a fire; a forever one's may be the
@@ -236,7 +285,8 @@ struct Dev {
     int32_t N, cap, n_int, n_flt, n_kind, n_rec, n_class;
     int32_t n_obj;   // object (NFGUID) properties: prop ids [n_if, n_if + n_obj), two words per entity
     int32_t n_if;    // n_int + n_flt: the first object property id
-    int32_t s_kstr;  // kind stride of s_hot / s_cold in records: cap + a pad (see kColPad)
+    int32_t s_kstr;  // kind stride of s_wide / s_cold in records: cap + a pad (see kColPad)
+    int32_t s_wstr;  // kind stride of s_word in words: cap + the same pad in bytes
     int64_t now;
     int32_t has_recops;
     int32_t has_pre;     // RemoveSchedule(self, name) calls are queued this frame (e_flags live)
@@ -245,8 +295,12 @@ struct Dev {
     // property words (see Tables::p_off / p_str)
     uint64_t* pmem;
     // schedules [kind][cap]
-    SchedHot* s_hot;
+    uint64_t* s_word;  // the scan's 8-byte word per (kind, slot): a compact record, or the flags of a wide one
+    SchedHot* s_wide;  // the record of a word with kScWide
     SchedCold* s_cold;
+    int64_t s_epoch;   // compact words count next from here (fixed at the world's first AddSchedule)
+    uint32_t s_kvalid; // kinds with a common step (fixed at the kind's first AddSchedule; 0 before any)
+    int32_t s_step[NFK_MAX_KINDS];  // the kinds' common steps in ms (28 bits, signed)
     uint8_t* e_flags;  // bit0: a RemoveSchedule(self, name) is queued (owns the remove-list key)
     // queued SetProperty* calls folded into (slot, property) GROUPS, sorted by (slot, property);
     // group g's calls are x_bits[x_first[g], x_first[g + 1]) in call order.  k_sets applies each

@@ -266,6 +266,10 @@ struct World {
     size_t xs_cap = 0;
     struct HOp { int32_t code; uint32_t slot, kind; float interval; int32_t count; int64_t time; };
     std::vector<HOp> hops;
+    // schedule words (nfgpu_device.hpp): the kinds still without a common step, and whether the
+    // epoch is fixed (fix_schedule_steps)
+    uint32_t s_unfixed = 0;
+    bool s_epoch_set = false;
 
     // pinned upload arena + device staging
     void* pin = nullptr;
@@ -2202,8 +2206,16 @@ int nfk_commit(void* world) {
         const char* ab = getenv("NFGPU_ABLATE");
         d.ablate = ab ? (uint32_t)strtoul(ab, nullptr, 0) : 0u;
     }
+    w->s_unfixed = 0;
+    w->s_epoch_set = false;
+    for (int k = 0; k < NK; k++)
+        if (w->kind_defined[k] && !(d.ablate & kAblSchedWide)) w->s_unfixed |= 1u << k;
     const int64_t cpad = kColPad / 8;  // column pad in values
     d.s_kstr = cap + (int32_t)(kColPad / (int64_t)sizeof(SchedHot));
+    d.s_wstr = cap + (int32_t)cpad;
+    d.s_epoch = 0;
+    d.s_kvalid = 0;
+    memset(d.s_step, 0, sizeof(d.s_step));
     ALLOC(d.pmem, ((size_t)cap + cpad) * (size_t)std::max(w->n_pw, 1) * 8);
     {
         int64_t off = 0;
@@ -2219,7 +2231,8 @@ int nfk_commit(void* world) {
             off += 2 * (int64_t)cap + cpad;
         }
     }
-    ALLOC(d.s_hot, (size_t)std::max(NK, 1) * d.s_kstr * sizeof(SchedHot));
+    ALLOC(d.s_word, (size_t)std::max(NK, 1) * d.s_wstr * 8);
+    ALLOC(d.s_wide, (size_t)std::max(NK, 1) * d.s_kstr * sizeof(SchedHot));
     ALLOC(d.s_cold, (size_t)std::max(NK, 1) * d.s_kstr * sizeof(SchedCold));
     ALLOC(d.e_flags, cap);
     ALLOC(d.ext_head, (size_t)cap * 4);
@@ -2341,7 +2354,8 @@ int nfk_commit(void* world) {
         HIPCHK(hipMemcpy(d.rcells[r], cells.data(), cells.size() * 8, hipMemcpyHostToDevice));
         HIPCHK(hipMemcpy(d.rused[r], used.data(), used.size() * 8, hipMemcpyHostToDevice));
     }
-    HIPCHK(hipMemset(d.s_hot, 0, (size_t)std::max(NK, 1) * d.s_kstr * sizeof(SchedHot)));
+    HIPCHK(hipMemset(d.s_word, 0, (size_t)std::max(NK, 1) * d.s_wstr * 8));
+    HIPCHK(hipMemset(d.s_wide, 0, (size_t)std::max(NK, 1) * d.s_kstr * sizeof(SchedHot)));
     HIPCHK(hipMemset(d.s_cold, 0, (size_t)std::max(NK, 1) * d.s_kstr * sizeof(SchedCold)));
     {
         std::vector<uint64_t> fd(cap, kDeadDesc);
@@ -3156,6 +3170,39 @@ int nfk_remove_all_schedules(void* world, int64_t gh, int64_t gd) {
     return NFK_OK;
 }
 
+// The schedule words' epoch and the kinds' common steps (nfgpu_device.hpp), taken from the queued
+// AddSchedule calls of the first window that has any for the kind: the epoch from the world's first
+// call, a kind's step the most frequent one among the window's calls for that kind (a majority
+// vote; the calls of a commit come in no particular order, and a rare odd interval among them
+// should not make every other record of the kind wide).  They are fixed here, before the frame
+// whose k_post_hostops writes the first record that uses them, and never change afterwards.  A
+// step that does not fit the hot record's 28 bits leaves its kind without one (its records are wide).
+static void fix_schedule_steps(World* w) {
+    Dev& d = w->d;
+    int64_t cand[NFK_MAX_KINDS] = {};
+    int64_t votes[NFK_MAX_KINDS] = {};
+    uint32_t seen = 0;
+    for (const auto& h : w->hops) {
+        if (h.code != 1 || !((w->s_unfixed >> h.kind) & 1u)) continue;
+        if (!w->s_epoch_set) {
+            d.s_epoch = (int64_t)((uint64_t)h.time - (uint64_t)kScEpochBack);
+            w->s_epoch_set = true;
+        }
+        const int64_t step = (int64_t)(h.interval * 1000.0f);
+        seen |= 1u << h.kind;
+        if (votes[h.kind] == 0) cand[h.kind] = step;
+        votes[h.kind] += cand[h.kind] == step ? 1 : -1;
+    }
+    for (int k = 0; k < NFK_MAX_KINDS; k++) {
+        if (!((seen >> k) & 1u)) continue;
+        w->s_unfixed &= ~(1u << k);
+        if (st_pack_step(cand[k])) {
+            d.s_step[k] = (int32_t)cand[k];
+            d.s_kvalid |= 1u << k;
+        }
+    }
+}
+
 // a batch of schedule calls, their objects resolved (see queue_sets)
 static int queue_schedule_calls(World* w, int32_t n, const int32_t* op, const int32_t* obj, const int32_t* kind,
                                 const float* interval, const int32_t* count, const int64_t* now_ms, const int64_t* gh,
@@ -3762,8 +3809,9 @@ int nfk_exist_schedule(void* world, int64_t gh, int64_t gd, int32_t kind, int32_
         HIPCHK(hipMemcpy(&word, w->ins_rows + (size_t)w->src_row[o] * w->row_words + w->n_pw + 4 * kind + 1, 8,
                          hipMemcpyDeviceToHost));
     } else if (w->slot_of_obj[o] >= 0) {
-        HIPCHK(hipMemcpy(&word, (const char*)(w->d.s_hot + (size_t)kind * w->d.s_kstr + w->slot_of_obj[o]) + 8, 8,
-                         hipMemcpyDeviceToHost));
+        // (the slot's schedule word: the present bit is bit 0 in either form)
+        HIPCHK(hipMemcpy(&word, w->d.s_word + (size_t)kind * w->d.s_wstr + w->slot_of_obj[o], 8, hipMemcpyDeviceToHost));
+        word <<= 32;
     }
     *exists = (int32_t)((word >> 32) & kStPresent);
     return NFK_OK;
@@ -4132,6 +4180,7 @@ static int execute_frame(World* w, int64_t now_ms, bool calls_only) {
     if (const char* inj = getenv("NFGPU_INJECT_EXEC_FAIL"); inj && inj[0] == '1')
         return drop_window(w, fail(NFK_ERR_CAPACITY, "injected failure after the membership changes"));
     if (w->cfg.n_obj) w->xops_h.resize(w->xops.size(), 0);
+    if (w->s_unfixed && !w->hops.empty()) fix_schedule_steps(w);
     Dev d = w->d;
     d.now = now_ms;
 
@@ -4715,8 +4764,8 @@ static int execute_frame(World* w, int64_t now_ms, bool calls_only) {
             hipLaunchKernelGGL(k_hfold<true>, dim3(gh_), dim3(256), 0, w->stream, (const uint64_t*)k2, (const uint32_t*)i2,
                                hc, (int32_t)nhq, cp, cq, (const uint32_t*)op, (const uint32_t*)oq, ps, po, hpost);
             hipLaunchKernelGGL(k_pre_hostops, dim3((unsigned)((npre + 255) / 256)), dim3(256), 0, w->stream,
-                               (const uint32_t*)ps, (const uint32_t*)po, (int32_t)npre, d.e_flags, d.s_hot, d.n_kind,
-                               d.s_kstr, (const uint32_t*)op + nhq);
+                               (const uint32_t*)ps, (const uint32_t*)po, (int32_t)npre, d.e_flags, d.s_word, d.n_kind,
+                               d.s_wstr, (const uint32_t*)op + nhq);
         }
         HIPCHK(hipGetLastError());
     }
@@ -5293,28 +5342,49 @@ int nfk_read_record(void* world, int32_t rec, uint64_t* cells) {
     return NFK_OK;
 }
 
+// the hot records [n_kind][n_objects] decoded from the schedule words, and which of them are wide
+static int read_schedules(World* w, int64_t* next_ms, int32_t* remain, uint8_t* state, uint8_t* wide) {
+    HIPCHK(hipStreamSynchronize(w->stream));
+    const Dev& d = w->d;
+    const int NK = d.n_kind;
+    std::vector<uint64_t> word((size_t)NK * d.s_wstr);
+    std::vector<SchedHot> hot((size_t)NK * d.s_kstr);
+    if (NK) HIPCHK(hipMemcpy(word.data(), d.s_word, word.size() * 8, hipMemcpyDeviceToHost));
+    if (NK) HIPCHK(hipMemcpy(hot.data(), d.s_wide, hot.size() * sizeof(SchedHot), hipMemcpyDeviceToHost));
+    for (int k = 0; k < NK; k++)
+        for (int32_t s = 0; s < d.N; s++) {
+            if (w->obj_of_slot[s] < 0) continue;
+            const size_t o = (size_t)k * w->n_obj + w->obj_of_slot[s];
+            const uint64_t x = word[(size_t)k * d.s_wstr + s];
+            if (!(x & kStPresent)) continue;
+            const SchedHot h = (x & kScWide) ? hot[(size_t)k * d.s_kstr + s] : sc_decode(x, d.s_epoch, d.s_step[k]);
+            if (state) {
+                state[o] = (uint8_t)(h.state & (kStPresent | kStForever));
+                next_ms[o] = h.next;
+                remain[o] = h.remain;
+            }
+            if (wide) wide[o] = (x & kScWide) ? 1 : 0;
+        }
+    return NFK_OK;
+}
+
 int nfk_read_schedules(void* world, int64_t* next_ms, int32_t* remain, uint8_t* state) {
     World* w = (World*)world;
     if (!w || !next_ms || !remain || !state) return fail(NFK_ERR_ARG, "null argument");
     if (!w->committed) return fail(NFK_ERR_STATE, "commit first");
-    HIPCHK(hipStreamSynchronize(w->stream));
-    const Dev& d = w->d;
-    const int NK = d.n_kind;
-    std::vector<SchedHot> hot((size_t)NK * d.s_kstr);
-    if (NK) HIPCHK(hipMemcpy(hot.data(), d.s_hot, hot.size() * sizeof(SchedHot), hipMemcpyDeviceToHost));
-    memset(state, 0, (size_t)NK * w->n_obj);
-    memset(next_ms, 0, (size_t)NK * w->n_obj * 8);
-    memset(remain, 0, (size_t)NK * w->n_obj * 4);
-    for (int k = 0; k < NK; k++)
-        for (int32_t s = 0; s < d.N; s++) {
-            if (w->obj_of_slot[s] < 0) continue;
-            size_t o = (size_t)k * w->n_obj + w->obj_of_slot[s], a = (size_t)k * d.s_kstr + s;
-            const SchedHot& h = hot[a];
-            state[o] = (uint8_t)(h.state & (kStPresent | kStForever));
-            next_ms[o] = (h.state & 1) ? h.next : 0;
-            remain[o] = (h.state & 1) ? h.remain : 0;
-        }
-    return NFK_OK;
+    const size_t n = (size_t)w->d.n_kind * w->n_obj;
+    memset(state, 0, n);
+    memset(next_ms, 0, n * 8);
+    memset(remain, 0, n * 4);
+    return read_schedules(w, next_ms, remain, state, nullptr);
+}
+
+int nfk_read_schedule_forms(void* world, uint8_t* wide) {
+    World* w = (World*)world;
+    if (!w || !wide) return fail(NFK_ERR_ARG, "null argument");
+    if (!w->committed) return fail(NFK_ERR_STATE, "commit first");
+    memset(wide, 0, (size_t)w->d.n_kind * w->n_obj);
+    return read_schedules(w, nullptr, nullptr, nullptr, wide);
 }
 
 int nfk_read_events(void* world, int32_t* ev_obj, int32_t* ev_pid, uint64_t* ev_old, uint64_t* ev_new) {

@@ -341,17 +341,33 @@ __global__ void k_hfold(const uint64_t* __restrict__ keys, const uint32_t* __res
     }
 }
 
+// The hot record of (kind k, slot s), whichever form its word has (no schedule: zeros).
+__device__ __forceinline__ SchedHot sched_get(const Dev& d, int k, size_t s) {
+    const uint64_t w = d.s_word[(size_t)k * d.s_wstr + s];
+    if (!(w & kStPresent)) return SchedHot{0, 0, 0u};
+    return (w & kScWide) ? d.s_wide[(size_t)k * d.s_kstr + s] : sc_decode(w, d.s_epoch, d.s_step[k]);
+}
+// Stores it: compact where sc_encode can, else the wide record and its flags; no schedule clears the word.
+__device__ __forceinline__ void sched_put(const Dev& d, int k, size_t s, const SchedHot& h) {
+    uint64_t w = sc_encode(h, d.s_epoch, d.s_step[k], (d.s_kvalid >> k) & 1u);
+    if (!w && (h.state & kStPresent)) {
+        d.s_wide[(size_t)k * d.s_kstr + s] = h;
+        w = sc_wide_word(h.state);
+    }
+    d.s_word[(size_t)k * d.s_wstr + s] = w;
+}
+
 // op: 1 = RemoveSchedule(self, name) queued (owns the remove-list key), 2 = RemoveSchedule(self);
 // n_dev: the entry count on the device (the device fold's), else n
 __global__ void k_pre_hostops(const uint32_t* __restrict__ slot, const uint32_t* __restrict__ op, int32_t n,
-                              uint8_t* __restrict__ e_flags, SchedHot* __restrict__ s_hot, int32_t n_kind,
-                              int32_t kstr, const uint32_t* __restrict__ n_dev) {
+                              uint8_t* __restrict__ e_flags, uint64_t* __restrict__ s_word, int32_t n_kind,
+                              int32_t wstr, const uint32_t* __restrict__ n_dev) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n || (n_dev && (uint32_t)i >= *n_dev)) return;
     const uint32_t s = slot[i];
     if (op[i] == 1) e_flags[s] |= 1;
     if (op[i] == 2)
-        for (int k = 0; k < n_kind; k++) s_hot[(size_t)k * kstr + s].state = 0;
+        for (int k = 0; k < n_kind; k++) s_word[(size_t)k * wstr + s] = 0;  // (a wide record is dead without its word)
 }
 
 // post-scan host ops, one entry per (slot, kind): bit0 remove, bit1 add (remove first), bit2 clear
@@ -368,15 +384,17 @@ __global__ void k_post_hostops(const uint32_t* __restrict__ slot, const uint32_t
         added[i] = 0;
         return;
     }
-    const size_t at = (size_t)kind[i] * d.s_kstr + s;
-    SchedHot h = d.s_hot[at];
-    if (op[i] & 1) h.state = 0;
+    const int k = (int)kind[i];
+    uint64_t& word = d.s_word[(size_t)k * d.s_wstr + s];
+    bool present = word & kStPresent;
+    if (op[i] & 1) present = false;
     if (op[i] & 4) d.e_flags[s] = 0;
-    added[i] = (op[i] & 2) && !(h.state & 1);
-    if ((op[i] & 2) && !(h.state & 1)) {  // AddSchedule (SM:218): an existing name wins
+    added[i] = (op[i] & 2) && !present;
+    if ((op[i] & 2) && !present) {  // AddSchedule (SM:218): an existing name wins
         const float f = interval[i];
         const int32_t c = count[i];
         const int64_t step = (int64_t)(f * 1000.0f);
+        SchedHot h;
         h.state = kStPresent | (c < 0 ? kStForever : 0u) | st_pack_step(step);
         h.next = time[i] + step;
         h.remain = c;
@@ -384,9 +402,10 @@ __global__ void k_post_hostops(const uint32_t* __restrict__ slot, const uint32_t
         cold.start = time[i];
         cold.all = c;
         cold.interval = f;
-        d.s_cold[at] = cold;
-    }
-    d.s_hot[at] = h;
+        d.s_cold[(size_t)k * d.s_kstr + s] = cold;
+        sched_put(d, k, s, h);
+    } else if (op[i] & 1)
+        word = 0;
 }
 
 // ---------------------------------------------------------------------------------
@@ -757,7 +776,7 @@ __global__ __launch_bounds__(kTPB) void k_tick_touch(Dev d) {
             const size_t at = fi0 + pfi;
             d.fi_slot[at] = (uint32_t)e;
             d.fi_kind[at] = (uint32_t)k;
-            d.fi_remain[at] = d.s_hot[(size_t)k * d.s_kstr + e].remain;
+            d.fi_remain[at] = sched_get(d, k, (size_t)e).remain;  // (a schedule the fire ended reads 0, its last remain)
             pfi++;
             en.bytes += 12;
         }
@@ -1901,10 +1920,9 @@ __device__ __forceinline__ uint64_t* row_word(const Dev& d, int32_t s, int w) {
     w -= d.n_if;
     if (w < 2 * d.n_obj) return prop_ptr(d, (uint32_t)(d.n_if + (w >> 1)), s) + (w & 1);  // (data, head)
     w -= 2 * d.n_obj;
-    if (w < 4 * d.n_kind) {
+    if (w < 4 * d.n_kind) {  // (the hot words, q < 2, are not stored as such: sched_row_word)
         const int k = w >> 2, q = w & 3;
-        return q < 2 ? (uint64_t*)&d.s_hot[(size_t)k * d.s_kstr + s] + q
-                     : (uint64_t*)&d.s_cold[(size_t)k * d.s_kstr + s] + (q - 2);
+        return q < 2 ? nullptr : (uint64_t*)&d.s_cold[(size_t)k * d.s_kstr + s] + (q - 2);
     }
     w -= 4 * d.n_kind;
     for (int r = 0; r < d.n_rec; r++) {
@@ -1916,12 +1934,28 @@ __device__ __forceinline__ uint64_t* row_word(const Dev& d, int32_t s, int w) {
     return nullptr;  // unreachable for w < row words
 }
 
+// Row word w as a schedule's hot word: its kind, or -1 when w is no hot word; q: which of the two.
+// The row keeps the wide record's two words (next, remain | state << 32) for either form of the
+// slot's word: k_pack decodes a compact word, k_unpack encodes where sc_encode can.
+__device__ __forceinline__ int sched_row_word(const Dev& d, int w, int& q) {
+    w -= d.n_if + 2 * d.n_obj;
+    q = w & 3;
+    return (w >= 0 && w < 4 * d.n_kind && q < 2) ? w >> 2 : -1;
+}
+
 __global__ __launch_bounds__(kTPB) void k_pack(Dev d, const int32_t* __restrict__ src, int32_t n, int32_t rw,
                                                uint64_t* __restrict__ rows) {
     const size_t total = (size_t)n * rw;
     for (size_t t = (size_t)blockIdx.x * kTPB + threadIdx.x; t < total; t += (size_t)gridDim.x * kTPB) {
         const int32_t i = (int32_t)(t % (size_t)n), w = (int32_t)(t / (size_t)n);
-        if (src[i] >= 0) rows[(size_t)i * rw + w] = *row_word(d, src[i], w);  // (-1: a row nobody reads)
+        if (src[i] < 0) continue;  // (-1: a row nobody reads)
+        int q;
+        const int k = sched_row_word(d, w, q);
+        if (k >= 0) {
+            const SchedHot h = sched_get(d, k, (size_t)src[i]);
+            rows[(size_t)i * rw + w] = q == 0 ? (uint64_t)h.next : (uint64_t)(uint32_t)h.remain | ((uint64_t)h.state << 32);
+        } else
+            rows[(size_t)i * rw + w] = *row_word(d, src[i], w);
     }
 }
 
@@ -1936,8 +1970,22 @@ __global__ __launch_bounds__(kTPB) void k_unpack(Dev d, const int32_t* __restric
         const int32_t i = (int32_t)(t % (size_t)n), w = (int32_t)(t / (size_t)n);
         const int64_t r = src[i];
         if (r == kKeepRow) continue;
-        const uint64_t x = r == kZeroRow ? 0ull : (r >= 0 ? mv[(size_t)r * rw + w] : ins[(size_t)(-1 - r) * rw + w]);
-        *row_word(d, dst[i], w) = x;
+        const uint64_t* const row = r == kZeroRow ? nullptr : (r >= 0 ? mv + (size_t)r * rw : ins + (size_t)(-1 - r) * rw);
+        int q;
+        const int k = sched_row_word(d, w, q);
+        if (k >= 0) {  // the thread of a hot record's first word stores the record, from both words
+            if (q == 0) {
+                SchedHot h{0, 0, 0u};
+                if (row) {
+                    h.next = (int64_t)row[w];
+                    h.remain = (int32_t)(uint32_t)row[w + 1];
+                    h.state = (uint32_t)(row[w + 1] >> 32);
+                }
+                sched_put(d, k, (size_t)dst[i], h);
+            }
+            continue;
+        }
+        *row_word(d, dst[i], w) = row ? row[w] : 0ull;
     }
 }
 

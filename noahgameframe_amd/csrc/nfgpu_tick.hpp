@@ -171,7 +171,7 @@ __device__ __forceinline__ unsigned long long block_excl_scan(unsigned long long
 // byte offset, so a column access is one saddr load on an offset shared by every column of the same
 // stride, with no 64-bit address arithmetic or 64-bit address registers per lane.
 // (The base goes through readfirstlane, which the compiler cannot see through: otherwise it
-// re-associates base_k = s_hot + k * stride with the lane offset into one 64-bit lane address per
+// re-associates base_k = s_word + k * stride with the lane offset into one 64-bit lane address per
 // kind.  Every base here is wave-uniform, so the first lane's is the base.)
 template <class S, typename T>
 __device__ __forceinline__ T* elem(T* base, uint32_t i, uint32_t str = 1) {
@@ -304,27 +304,67 @@ constexpr int kWavesJit = 5;  // the hipRTC specialisation (nfgpu_jit.hpp; profi
 constexpr long long kMsgStrideLimit = 1ll << 30;  // fixed-stride message runs: at most 4 GiB reserved
 
 template <class S>
-__device__ __forceinline__ void sched_load(const Dev& d, int e, int k0, SchedHot (&h)[kKindChunk]) {
-    // kinds past n_kind re-read the chunk's first record (a cache hit); a static schema loads
+__device__ __forceinline__ void sched_load(const Dev& d, int e, int k0, uint64_t (&h)[kKindChunk]) {
+    // kinds past n_kind re-read the chunk's first word (a cache hit); a static schema loads
     // exactly its kinds
     const int nk = S::n_kind(d) - k0;
 #pragma unroll
     for (int j = 0; j < kKindChunk; j++)
         if (!S::kStatic || j < nk)
-            h[j] = ld_nt<(S::kNt & kNtSchedLoad) != 0>(elem<S>(d.s_hot + (size_t)(k0 + (j < nk ? j : 0)) * d.s_kstr, (uint32_t)e));
+            h[j] = ld_nt<(S::kNt & kNtSchedLoad) != 0>(elem<S>(d.s_word + (size_t)(k0 + (j < nk ? j : 0)) * d.s_wstr, (uint32_t)e));
+}
+// One due-test and fire of a WIDE record (the word has kScWide): NFCScheduleModule::Execute's
+// reschedule on the 16-byte hot record, the cold record where the hot one cannot give the next
+// time.  Returns whether it fired; gone: the fire removed the schedule (the caller clears the word).
+template <class S, bool kStore>
+__device__ __forceinline__ bool sched_fire_wide(const Dev& d, int e, int k, unsigned& bytes, bool& taken, int32_t& remain,
+                                                bool& gone) {
+    SchedHot* const at = elem<S>(d.s_wide + (size_t)k * d.s_kstr, (uint32_t)e);
+    SchedHot h = *at;
+    bytes += 16;
+    if (!(d.now > h.next)) return false;
+    const bool forever = h.state & kStForever;
+    if (!(h.remain > 0 || forever)) return false;
+    h.remain -= 1;
+    const uint32_t st = h.state;
+    if (h.remain <= 0 && !forever) {
+        if (!taken) {  // insert into the remove list succeeds for the first one only
+            h.state = 0;
+            taken = true;
+            gone = true;
+        }
+    } else {
+        const bool first = !(st & kStFired);
+        if ((st & kStStep) && (first || !forever || h.remain < 0)) {
+            // next = start + step * (all - remain) without the cold record (see kSt*)
+            if (!first) h.next += st_step(st);
+        } else {
+            const SchedCold c = *elem<S>(d.s_cold + (size_t)k * d.s_kstr, (uint32_t)e);
+            bytes += 16;
+            const int64_t step = (int64_t)(c.interval * 1000.0f);
+            const int32_t done = (int32_t)((uint32_t)c.all - (uint32_t)h.remain);
+            h.next = c.start + step * (int64_t)done;
+        }
+        h.state = st | kStFired;
+    }
+    remain = h.remain;
+    bytes += 16;
+    if (kStore && !(d.ablate & kAblNoSchedStore)) *at = h;
+    return true;
 }
 // NFCScheduleModule::Execute (SM:51-81) for one object: its schedules in name order (kind id
-// order).  The hot records of a chunk of kinds are loaded together (independent 16 B loads).
-// Rescheduled / removed records are stored back.  Every load is issued without a branch and before
-// the first use of any of them: a load under a branch is followed by a wait at the join, and a
-// first use after the record stores would make the wave wait for the stores too (the vector
-// memory counter retires in order), i.e. one round trip per kind or per store batch.
+// order).  The 8-byte words of a chunk of kinds are loaded together (independent loads).
+// Rescheduled / removed records are stored back.  Every load of the compact path is issued without
+// a branch and before the first use of any of them: a load under a branch is followed by a wait at
+// the join, and a first use after the record stores would make the wave wait for the stores too
+// (the vector memory counter retires in order), i.e. one round trip per kind or per store batch.
+// (A wide record is such a load under a branch: the price of the fallback.)
 // kStore = false: the fire test only (k_chain re-runs it before k_tick; nothing is stored).
 template <class S, bool kFirst, bool kStore = true>
 __device__ __forceinline__ void sched_chunk(const Dev& d, int e, int k0, unsigned& bytes, uint64_t& desc,
                                             bool& dead, bool& taken, uint32_t& fired, int32_t* s_rem,
                                             bool oob) {
-    SchedHot h[kKindChunk];
+    uint64_t h[kKindChunk];
     uint8_t ef = 0;
     sched_load<S>(d, e, k0, h);
     if constexpr (kFirst) {
@@ -341,40 +381,54 @@ __device__ __forceinline__ void sched_chunk(const Dev& d, int e, int k0, unsigne
     for (int j = 0; j < kKindChunk; j++) {
         const int k = k0 + j;
         if (k >= S::n_kind(d)) break;
-        bytes += 16;
+        bytes += 8;
         bool fire = false;
-        if (!dead && (h[j].state & kStPresent) && d.now > h[j].next) {
-            const bool forever = h[j].state & kStForever;
-            if (h[j].remain > 0 || forever) {
-                fire = true;
-                h[j].remain -= 1;
-                fired |= 1u << k;
-                const uint32_t st = h[j].state;
-                if (h[j].remain <= 0 && !forever) {
-                    if (!taken) {  // insert into the remove list succeeds for the first one only
-                        h[j].state = 0;
-                        taken = true;
-                    }
-                } else {
-                    const bool first = !(st & kStFired);
-                    if ((st & kStStep) && (first || !forever || h[j].remain < 0)) {
-                        // next = start + step * (all - remain) without the cold record (see kSt*)
-                        if (!first) h[j].next += st_step(st);
+        uint64_t w = h[j];
+        int32_t remain = 0;
+        if (!dead && (w & kStPresent)) {
+            if (w & kScWide) {
+                bool gone = false;
+                fire = sched_fire_wide<S, kStore>(d, e, k, bytes, taken, remain, gone);
+                if (fire) fired |= 1u << k;
+                if (fire && s_rem) s_rem[k * kTPB + threadIdx.x] = remain;  // for the fired list
+                fire = gone;  // the word changes only when the schedule is removed
+                w = 0;
+            } else if (d.now > d.s_epoch + sc_off(w)) {  // (a compact word exists only once the epoch is fixed)
+                const bool forever = w & kStForever;
+                remain = sc_remain(w);
+                if (remain > 0 || forever) {
+                    fire = true;
+                    remain -= 1;
+                    fired |= 1u << k;
+                    if (remain <= 0 && !forever) {
+                        if (!taken) {  // insert into the remove list succeeds for the first one only
+                            w = 0;
+                            taken = true;
+                        } else
+                            w = sc_word((uint32_t)w, sc_off(w), remain);
                     } else {
-                        const SchedCold c = *elem<S>(d.s_cold + (size_t)k * d.s_kstr, (uint32_t)e);
-                        bytes += 16;
-                        const int64_t step = (int64_t)(c.interval * 1000.0f);
-                        const int32_t done = (int32_t)((uint32_t)c.all - (uint32_t)h[j].remain);
-                        h[j].next = c.start + step * (int64_t)done;
+                        // next = start + step * (all - remain): the first fire leaves next, later ones add the step
+                        const int64_t off = sc_off(w) + ((w & kStFired) ? (int64_t)d.s_step[k] : 0ll);
+                        const uint32_t fl = (uint32_t)w | kStFired;
+                        if (sc_fits(off, remain))
+                            w = sc_word(fl, off, remain);
+                        else {  // out of the word's fields: the record goes wide, for good
+                            SchedHot x;
+                            x.next = d.s_epoch + off;
+                            x.remain = remain;
+                            x.state = (fl & 7u) | st_pack_step((int64_t)d.s_step[k]);
+                            if (kStore && !(d.ablate & kAblNoSchedStore)) *elem<S>(d.s_wide + (size_t)k * d.s_kstr, (uint32_t)e) = x;
+                            bytes += 16;
+                            w = sc_wide_word(x.state);
+                        }
                     }
-                    h[j].state = st | kStFired;
+                    if (s_rem) s_rem[k * kTPB + threadIdx.x] = remain;  // for the fired list
                 }
-                if (s_rem) s_rem[k * kTPB + threadIdx.x] = h[j].remain;  // for the fired list
-                bytes += 16;
             }
         }
+        if (fire) bytes += 8;
         if (kStore && fire && !(d.ablate & kAblNoSchedStore))
-            st_nt<(S::kNt & kNtStateStore) != 0>(elem<S>(d.s_hot + (size_t)k * d.s_kstr, (uint32_t)e), h[j]);
+            st_nt<(S::kNt & kNtStateStore) != 0>(elem<S>(d.s_word + (size_t)k * d.s_wstr, (uint32_t)e), w);
     }
 }
 // Loads desc = fan_desc[e] with the first chunk; returns the fired-kind mask.  oob: a slot past N
@@ -836,9 +890,10 @@ __device__ __forceinline__ void emit_fired(const Dev& d, TickSt& t, const int32_
         const int32_t rem = s_rem[k * kTPB + threadIdx.x];
         // (a forever heartbeat's remain may be any int32, the sentinel too: sched_edges worlds
         // wrap it through INT32_MIN; a counted one is >= 0 after a fire.  The forever bit is the
-        // same before and after the scan, so the record's state is read whatever the L1 holds)
+        // same before and after the scan, in a compact word and in a wide one's, so the word is read
+        // whatever the L1 holds)
         if ((d.ablate & kAblCheckRem) && rem == kRemUnset &&
-            !(elem<S>(d.s_hot + (size_t)k * d.s_kstr, (uint32_t)e)->state & kStForever))
+            !(*elem<S>(d.s_word + (size_t)k * d.s_wstr, (uint32_t)e) & kStForever))
             dev_error(d, kErrRemain);
         if (!(d.ablate & kAblNoFiStore)) {
             st_off_nt<kNE>(t_fis, pfi, (uint32_t)e);

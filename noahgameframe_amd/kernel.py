@@ -125,6 +125,7 @@ def load_library(path=LIB_PATH):
         "nfk_get_props": [VP, I32, VP, VP, VP, VP], "nfk_exist_schedule": [VP, I64, I64, I32, VP],
         "nfk_execute": [VP, I64], "nfk_execute_calls": [VP], "nfk_summary_get": [VP, P(Summary)], "nfk_outputs_get": [VP, P(Outputs)],
         "nfk_read_prop": [VP, I32, VP], "nfk_read_record": [VP, I32, VP], "nfk_read_schedules": [VP, VP, VP, VP],
+        "nfk_read_schedule_forms": [VP, VP],
         "nfk_read_events": [VP, VP, VP, VP, VP], "nfk_read_rec_events": [VP, VP, VP, VP, VP],
         "nfk_read_fired": [VP, VP, VP, VP], "nfk_read_fanout": [VP, VP, VP],
         "nfk_set_profiling": [VP, I32], "nfk_kernel_times": [VP, VP, VP, VP], "nfk_reset_kernel_times": [VP],
@@ -856,6 +857,12 @@ class NFKernelModule:
         st = np.zeros((self.n_kind, self.n_obj), np.uint8)
         self._chk(self.lib.nfk_read_schedules(self.h, _p(nx), _p(rm), _p(st)))
         return nx, rm, st
+
+    def read_schedule_forms(self):
+        """[n_kind][n_obj] uint8: 1 where the schedule's device record is wide, 0 compact or absent."""
+        wide = np.zeros((self.n_kind, self.n_obj), np.uint8)
+        self._chk(self.lib.nfk_read_schedule_forms(self.h, _p(wide)))
+        return wide
 
     def read_tick(self):
         """All outputs of the last frame, entities as object (creation) indices."""

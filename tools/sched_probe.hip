@@ -8,6 +8,9 @@
 //   noscan   the fired list at per-thread fixed slots (no block scan, no barrier)
 //   loads    the loads and the fire test only (one word per thread written)
 //   stream   the same bytes as 'full' as a grid-stride stream of 16-byte loads and stores
+//   c8_*     full / nolist / loads on 8-byte records (flags 4 bits, next as a 33-bit offset from an
+//            epoch, remain 27 bits; the step a kernel argument): [kind][slot] arrays kColPad apart,
+//            the same fire rates, 8-byte stores for the fired ones
 // Prints one JSON line per case (best and median us of 20 launches).
 #include <hip/hip_runtime.h>
 
@@ -148,6 +151,66 @@ __global__ __launch_bounds__(kTPB) void scan(P p) {
     }
 }
 
+// The same scan on 8-byte records: word = flags | offset << 4 | remain << 37.
+struct P8 {
+    uint64_t* hot;
+    int64_t kstr;
+    int64_t rel;   // now - epoch
+    int64_t step;  // the kinds' common step
+};
+template <int kMode>  // 0 full, 1 nolist, 3 loads
+__global__ __launch_bounds__(kTPB) void scan8(P p, P8 q) {
+    __shared__ int32_t s_rem[kK * kTPB];
+    __shared__ uint32_t s_w[4];
+    const uint32_t e = blockIdx.x * kTPB + threadIdx.x;
+    uint64_t h[kK];
+#pragma unroll
+    for (int k = 0; k < kK; k++) h[k] = __builtin_nontemporal_load(q.hot + (size_t)k * q.kstr + e);
+    const uint64_t desc = __builtin_nontemporal_load(p.desc + e);
+    uint32_t fired = 0;
+#pragma unroll
+    for (int k = 0; k < kK; k++) {
+        const int64_t off = (int64_t)((h[k] >> 4) & ((1ull << 33) - 1));
+        if ((desc >> 63) || !(h[k] & 1) || !(q.rel > off)) continue;
+        const int32_t rem = (int32_t)((int64_t)h[k] >> 37) - 1;
+        fired |= 1u << k;
+        const uint64_t x = (h[k] & 15u) | ((uint64_t)(off + q.step) << 4) | ((uint64_t)(int64_t)rem << 37);
+        if (kMode <= 2) q.hot[(size_t)k * q.kstr + e] = x;
+        s_rem[k * kTPB + threadIdx.x] = rem;
+    }
+    if (kMode == 3) {
+        if (fired == 0xFFFFFFFFu) p.sink[e] = fired;
+        return;
+    }
+    if (kMode == 1) return;
+    const uint32_t nf = __builtin_popcount(fired);
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    uint32_t inc = nf;
+    for (int d = 1; d < 64; d <<= 1) {
+        const uint32_t t = __shfl_up(inc, d, 64);
+        if (lane >= d) inc += t;
+    }
+    if (lane == 63) s_w[w] = inc;
+    __syncthreads();
+    uint32_t before = 0, tot = 0;
+    for (int i = 0; i < 4; i++) {
+        before += i < w ? s_w[i] : 0u;
+        tot += s_w[i];
+    }
+    uint32_t pos = before + inc - nf;
+    if (threadIdx.x == 0) p.t_fi[blockIdx.x] = tot;
+    const size_t b = (size_t)blockIdx.x * p.fi_tcap;
+    uint32_t f = fired;
+    while (f) {
+        const int k = __builtin_ctz(f);
+        f &= f - 1;
+        p.fi_slot[b + pos] = e;
+        p.fi_kind[b + pos] = k;
+        p.fi_rem[b + pos] = s_rem[k * kTPB + threadIdx.x];
+        pos++;
+    }
+}
+
 __global__ __launch_bounds__(256) void stream(const u32x4* __restrict__ r, size_t nr, u32x4* __restrict__ w, size_t nw) {
     const size_t stride = (size_t)gridDim.x * 256;
     uint32_t acc = 0;
@@ -176,6 +239,18 @@ int main() {
             hot[(size_t)k * kstr + i] = r;
             for (int lay = 0; lay < 3; lay++) hot_lay[lay][rec_at(lay, kstr, k, (uint32_t)i)] = r;
         }
+    // the 8-byte records of the same schedules: due = offset 0 (now - epoch = 1), else the top offset
+    P8 q;
+    q.kstr = N + 2304 / 8;
+    q.rel = 1;
+    q.step = 0;
+    std::vector<uint64_t> hot8((size_t)kK * q.kstr, 0);
+    for (int k = 0; k < kK; k++)
+        for (int i = 0; i < N; i++) {
+            const bool due = hot[(size_t)k * kstr + i].next == 0;
+            hot8[(size_t)k * q.kstr + i] = 3u | ((due ? 0ull : (1ull << 33) - 1) << 4) | ((uint64_t)(int64_t)-1 << 37);
+        }
+    CK(hipMalloc(&q.hot, hot8.size() * 8));
     P p;
     CK(hipMalloc(&p.hot, hot.size() * sizeof(Rec)));
     CK(hipMemcpy(p.hot, hot.data(), hot.size() * sizeof(Rec), hipMemcpyHostToDevice));
@@ -200,13 +275,15 @@ int main() {
     hipEvent_t a, b;
     CK(hipEventCreate(&a));
     CK(hipEventCreate(&b));
-    const char* names[21] = {"full", "nolist", "noscan", "loads", "stream", "nolist_plainld", "nolist_ntst",
+    const char* names[24] = {"full", "nolist", "noscan", "loads", "stream", "nolist_plainld", "nolist_ntst",
                              "nolist_shadow", "nolist_plainld_ntst", "nolist_dense_kind_only", "nolist_all_records",
                              "nolist_all_records_plainld", "nolist_sector32", "nolist_sector64", "nolist_line128",
-                             "aos5_nolist", "aos5_loads", "aos5_full", "hyb_nolist", "hyb_loads", "hyb_full"};
-    for (int m = 0; m < 21; m++) {
+                             "aos5_nolist", "aos5_loads", "aos5_full", "hyb_nolist", "hyb_loads", "hyb_full",
+                             "c8_full", "c8_nolist", "c8_loads"};
+    for (int m = 0; m < 24; m++) {
         const int lay = m >= 18 ? 2 : m >= 15 ? 1 : 0;  // the records in the case's layout
         CK(hipMemcpy(p.hot, hot_lay[lay].data(), hot.size() * sizeof(Rec), hipMemcpyHostToDevice));
+        if (m >= 21) CK(hipMemcpy(q.hot, hot8.data(), hot8.size() * 8, hipMemcpyHostToDevice));
         std::vector<float> t;
         for (int it = 0; it < 22; it++) {
             CK(hipEventRecord(a));
@@ -231,6 +308,9 @@ int main() {
             if (m == 18) scan<1, true, 0, 2><<<T, kTPB>>>(p);
             if (m == 19) scan<3, true, 0, 2><<<T, kTPB>>>(p);
             if (m == 20) scan<0, true, 0, 2><<<T, kTPB>>>(p);
+            if (m == 21) scan8<0><<<T, kTPB>>>(p, q);
+            if (m == 22) scan8<1><<<T, kTPB>>>(p, q);
+            if (m == 23) scan8<3><<<T, kTPB>>>(p, q);
             CK(hipEventRecord(b));
             CK(hipEventSynchronize(b));
             float ms;
@@ -239,7 +319,7 @@ int main() {
         }
         std::sort(t.begin(), t.end());
         printf("{\"case\": \"%s\", \"best_us\": %.1f, \"median_us\": %.1f, \"MB\": %.0f}\n", names[m], t[0], t[t.size() / 2],
-               (rd + wr) / 1e6);
+               (m >= 21 ? (double)N * (kK * 8 + 8) + (double)N * 1.32 * (8 + 12) : rd + wr) / 1e6);
     }
     return 0;
 }
