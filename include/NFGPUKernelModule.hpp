@@ -343,6 +343,12 @@ public:
     };
 
     // ---- schema (what NFIClassModule loads from Struct/Class/*.xml) ----
+    // LAYOUT POLICY.  Programs hold a module by value (the reference-side adapter, integration/
+    // NFGPUKernelPlugin.cpp, embeds one; its sessions under oracle/_ref/ run prebuilt on a machine without
+    // the reference tree) and run on whatever libnfgpu_plugin.so is installed beside them.  From the first
+    // release with this note on, a change to this class adds no data member and no virtual function, and
+    // reorders none: new state lives in NFGPUKernelModule.cpp, keyed by the module (LinkRecordColumns'
+    // does), until a release that is declared to break the layout moves it in.
     explicit NFGPUKernelModule(int capacity, void* hip_stream = nullptr);
     ~NFGPUKernelModule();
     int AddProperty(const std::string& name, TDATA_TYPE type);  // TDATA_INT / FLOAT / OBJECT; returns its index
@@ -449,6 +455,19 @@ public:
     // record event with the frame: nOpType = Swap, nRow = origin, nCol = target ROW, empty values.
     // The entry point is looked up at first use; a library without it: std::runtime_error.
     bool SwapRowInfo(const NFGUID& self, const std::string& strRecordName, int nOriginRow, int nTargetRow);
+    // NFCPropertyModule::OnRecordPropertyEvent (NFCPropertyModule.cpp:127-149) as part of the schema
+    // (nfk_link_record): after every record event of the record, the int property named for the event's
+    // nCol takes the 32-bit sum of that column over the record's first `rows` rows — an accepted Set names
+    // its column, AddRow / RemoveRow / ClearRecord column 0, SwapRowInfo the column whose index is its
+    // target row.  propertyNames: one per LOGICAL column, "" for a column without a link.  Before
+    // AfterInit, which hands the links to the world (a column that is not an int column, a name that is
+    // no int property or is linked twice: AfterInit throws with the library's message).  Afterwards
+    // SetPropertyInt of a linked name returns false and queues nothing — the one difference from the
+    // reference, whose SetPropertyValue(..., NPG_ALL, ...) writes the property directly — and
+    // GetPropertyInt replays the window's queued calls on the record (nfk_get_props).  A record with an
+    // object column cannot be linked (std::invalid_argument): a Swap event names the column whose index is
+    // its target row, which is the reference's logical column and the device's physical one.
+    void LinkRecordColumns(const std::string& strRecordName, int rows, const std::vector<std::string>& propertyNames);
     bool IsUsed(const NFGUID& self, const std::string& strRecordName, int nRow);
     // NFIKernelModule::GetRecordInt / GetRecordFloat (NFIKernelModule.h:134-135): read-your-writes
     // like GetProperty*; 0 for an unused row (NFCRecord::GetInt, RC:623)

@@ -373,6 +373,55 @@ int nfk_record_rows(void* world, int32_t n, const int64_t* guid_head, const int6
 int nfk_swap_rows(void* world, int32_t n, const int64_t* guid_head, const int64_t* guid_data, const int32_t* rec,
                   const int32_t* row_origin, const int32_t* row_target);
 
+/* ---- property links: record columns summed into properties ----
+ * NFCPropertyModule::OnRecordPropertyEvent (NFCPropertyModule.cpp:127-149) as part of the schema: the
+ * reference's game server registers it on every player's CommPropertyValue record (one row per
+ * property group, one column per combat property), and it is how MAXHP and its like change at all.
+ * A link (rows, col_pid[cols]) on record rec says: after EVERY record event the reference raises on
+ * rec for an object, with c the event's nCol field and col_pid[c] >= 0,
+ *     sum = 0 (32 bits); for i in [0, min(rows, the record's rows)): sum += (int32) GetInt(i, c)
+ *     SetPropertyInt(self, col_pid[c], sum)          (stored only when different, PR:254)
+ * where GetInt is 0 for a row the record does not use at that instant (RC:616-635).  nCol and the
+ * instant of each event:
+ *   Update (an accepted nfk_set_records call; a refused or unchanged Set raises nothing, RC:194 /
+ *           RC:209): nCol the cell's column; the sum after the store.
+ *   Add / Cover (nfk_record_rows op 1, RC:111-180): nCol 0; after the row's values are written and the
+ *           row is used.  The values AddRow writes to OTHER columns raise nothing, so those columns'
+ *           properties go stale until an event names them: the reference's behaviour and this one's.
+ *   Del (op 2, and each step of op 3 ClearRecord, last row first; RC:1086-1117): nCol 0; BEFORE the
+ *           used bit is cleared, so the removed row still counts.
+ *   Swap (nfk_swap_rows, RC:1219-1253): nCol is the TARGET ROW's index; the sum is over column number
+ *           `target`, after the exchange; nothing when `target` is no column or that column has no link.
+ *           (`target` counts PHYSICAL columns, as every column of this interface does; the reference counts
+ *           logical ones, which differs in a record with an object column ahead of column `target`.)
+ * Each cell is truncated to int32 before the add (2^32 + 5 counts as 5).  The reference's add is a
+ * signed int add; the device's wraps modulo 2^32 and the result is sign-extended to the property's 64
+ * bits.  (The two agree wherever the signed add does not overflow; the wrap is pinned on the tests'
+ * model only.)
+ * The links run on the device in the window's call order (k_rrows; k_links stores the sums): the
+ * property's value after the window is the sum at the last such event, and the frame reports ONE
+ * property event, frame-start value -> final value, dropped when equal, in the entity's events in
+ * property-id order with the property's own flags and recipients, like a standalone queued Set.
+ * A heartbeat program that reads the property (an operand, NFK_*_PROP, a guard) sees the window's
+ * value in the same frame.  nfk_execute and nfk_execute_calls both apply links.
+ * A linked property belongs to its link: nfk_load_prop, nfk_spawn_objects' values and imports set its
+ * stored value as before, but a queued direct Set of it (nfk_set_props / nfk_set_props_obj) is
+ * NFK_ERR_ARG and the batch queues nothing — the one difference from the reference, whose
+ * SetPropertyValue(..., NPG_ALL, ...) writes the property directly.  nfk_get_props, nfk_query_objects
+ * and nfk_snapshot_objects see the window's queued calls on the record (read-your-writes: the list
+ * is replayed on the host from the device's used mask and the one column).
+ * col_pid: [the record's cols], -1 for a column without a link; NULL removes the record's link.
+ * Before nfk_commit only (NFK_ERR_STATE after).  NFK_ERR_ARG: a null world, a bad record, a mode that
+ * is not NFK_LINK_SUM32, rows outside [1, the record's rows], a linked column that is not NFK_REC_INT,
+ * a pid that is not an int property, a pid linked from two places, a pid that is one of
+ * nfk_set_scene_props' properties (in whichever order the two calls come); nothing is changed then.
+ * nfk_commit is NFK_ERR_ARG when a heartbeat program writes a linked property or a record op
+ * (RIADD_CLAMP / RFAFFINE) targets a linked (record, column); NFK_GUARD_CELL guards on linked cells
+ * stay legal. */
+#define NFK_LINK_SUM32 0
+int nfk_link_record(void* world, int32_t rec, int32_t rows, const int32_t* col_pid /* [cols], -1: none; NULL: unlink */,
+                    int32_t mode /* NFK_LINK_SUM32 */);
+
 /* NFCRecord::IsUsed (RC:1209) for n (object, record) pairs: the used-row masks as the reference holds
  * them now — the device's after the last frame (one read per pair per window, cached until the next
  * nfk_execute) with this window's queued row operations replayed in call order.  What AddRow(-1)

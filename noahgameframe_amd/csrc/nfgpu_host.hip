@@ -136,6 +136,16 @@ struct World {
     std::vector<std::vector<uint64_t>> init_rcells, init_rused;
     std::vector<bool> rec_defined;
     uint8_t rec_ctype[NFK_MAX_RECORDS][NFK_MAX_REC_COLS] = {};  // NFK_REC_*
+    // property links (nfk_link_record): per record the rows summed (0: no link) and each column's
+    // int property (-1: none), the linked properties as a mask, and the frame's hit masks and sums
+    // (LinkDev, the third argument of k_rrows and k_links' own)
+    int8_t lk_rows[NFK_MAX_RECORDS] = {};
+    int8_t lk_pid[NFK_MAX_RECORDS][NFK_MAX_REC_COLS];
+    uint64_t lk_pids[2] = {0, 0};
+    void* lk_buf = nullptr;
+    size_t lk_cap = 0;
+    int16_t lk_of_pid[128];  // a linked property's rec << 4 | col (link_pid_mask keeps it), else -1
+    bool linked_pid(int32_t p) const { return p >= 0 && p < 128 && ((lk_pids[p >> 6] >> (p & 63)) & 1); }
 
     Tables tab{};
     bool kind_defined[NFK_MAX_KINDS] = {};
@@ -242,6 +252,8 @@ struct World {
     std::vector<uint64_t> rvals;  // AddRow values, NFK_MAX_REC_COLS words each
     std::unordered_map<uint64_t, std::vector<uint32_t>> rq_index;  // (object << 3 | record) -> its queued calls
     std::unordered_map<uint64_t, uint64_t> ucache;  // (object << 3 | record) -> used mask read this window
+    // (object << 7 | linked property) -> its column's cells in row order, read this window (current_props)
+    std::unordered_map<uint64_t, std::vector<uint64_t>> lcache;
     std::vector<uint64_t> rowpairs;  // (slot << 3 | record) with row operations this window (nfk_execute)
     void* rl_buf = nullptr;          // rs_has / rl_cnt / rl_ev
     size_t rl_cap = 0;
@@ -412,6 +424,7 @@ int drop_window(World* w, int r) {
     w->rvals.clear();
     w->rq_index.clear();
     w->ucache.clear();
+    w->lcache.clear();
     w->dcache.clear();
     w->ov_last.clear();
     w->ov_prev.clear();
@@ -1856,6 +1869,8 @@ int nfk_create(const nfk_config* cfg, void** out) {
     w->init_rcells.resize(cfg->n_rec);
     w->init_rused.resize(cfg->n_rec);
     w->rec_defined.assign(cfg->n_rec, false);
+    memset(w->lk_pid, 0xFF, sizeof(w->lk_pid));
+    memset(w->lk_of_pid, 0xFF, sizeof(w->lk_of_pid));
     *out = w;
     return NFK_OK;
 }
@@ -1887,6 +1902,7 @@ int nfk_destroy(void* world) {
     if (w->rs_buf) (void)hipFree(w->rs_buf);
     if (w->rss_buf) (void)hipFree(w->rss_buf);
     if (w->rl_buf) (void)hipFree(w->rl_buf);
+    if (w->lk_buf) (void)hipFree(w->lk_buf);
     if (w->look_stream) (void)hipStreamSynchronize(w->look_stream);
     if (w->guid_d) (void)hipFree(w->guid_d);
     if (w->look_dev) (void)hipFree(w->look_dev);
@@ -1965,6 +1981,57 @@ int nfk_define_record(void* world, int32_t rec, int32_t rows, int32_t cols, cons
     for (int c = 0; c < w->cfg.n_class; c++) w->tab.rflags[c][rec] = flags_per_class[c];
     for (int c = 0; c < NFK_MAX_REC_COLS; c++) w->rec_ctype[rec][c] = col_types && c < cols ? col_types[c] : 0;
     w->rec_defined[rec] = true;
+    return NFK_OK;
+}
+
+// the linked properties of every record but `skip` (-1: of all of them)
+static void link_pid_mask(World* w, int skip, uint64_t m[2]) {
+    m[0] = m[1] = 0;
+    if (skip < 0) {
+        memset(w->lk_of_pid, 0xFF, sizeof(w->lk_of_pid));
+        for (int r = 0; r < w->cfg.n_rec; r++)
+            for (int c = 0; w->lk_rows[r] && c < NFK_MAX_REC_COLS; c++)
+                if (w->lk_pid[r][c] >= 0) w->lk_of_pid[w->lk_pid[r][c]] = (int16_t)(r << 4 | c);
+    }
+    for (int r = 0; r < w->cfg.n_rec; r++)
+        for (int c = 0; r != skip && w->lk_rows[r] && c < NFK_MAX_REC_COLS; c++)
+            if (w->lk_pid[r][c] >= 0) m[w->lk_pid[r][c] >> 6] |= 1ull << (w->lk_pid[r][c] & 63);
+}
+
+// NFCPropertyModule::OnRecordPropertyEvent (PM:127-149) as part of the schema: after every record
+// event of record rec, the int property col_pid[nCol] takes the 32-bit sum of column nCol over the
+// record's first `rows` rows (nfgpu.h states the events' nCol).  Applied by k_rrows / k_links.
+int nfk_link_record(void* world, int32_t rec, int32_t rows, const int32_t* col_pid, int32_t mode) {
+    World* w = (World*)world;
+    if (!w) return fail(NFK_ERR_ARG, "null world");
+    if (w->committed) return fail(NFK_ERR_STATE, "schema is fixed after commit");
+    if (rec < 0 || rec >= w->cfg.n_rec || !w->rec_defined[rec]) return fail(NFK_ERR_ARG, "nfk_link_record: bad record");
+    if (col_pid) {
+        if (mode != NFK_LINK_SUM32) return fail(NFK_ERR_ARG, "nfk_link_record: mode must be NFK_LINK_SUM32");
+        if (rows < 1 || rows > w->tab.rec_rows[rec])
+            return fail(NFK_ERR_ARG, "nfk_link_record: rows outside [1, the record's rows]");
+    }
+    uint64_t other[2], mine[2] = {0, 0};
+    link_pid_mask(w, rec, other);
+    const int cols = w->tab.rec_cols[rec];
+    for (int c = 0; col_pid && c < cols; c++) {
+        const int32_t p = col_pid[c];
+        if (p == -1) continue;
+        if (p < 0 || p >= w->cfg.n_int)
+            return fail(NFK_ERR_ARG, "nfk_link_record: column " + std::to_string(c) + " links something that is not an int property");
+        if (w->rec_ctype[rec][c] != NFK_REC_INT)
+            return fail(NFK_ERR_ARG, "nfk_link_record: column " + std::to_string(c) + " is not an int column");
+        if (((other[p >> 6] | mine[p >> 6]) >> (p & 63)) & 1)
+            return fail(NFK_ERR_ARG, "nfk_link_record: property " + std::to_string(p) + " is linked from two places");
+        if (p == w->pid_scene || p == w->pid_group)
+            return fail(NFK_ERR_ARG, "nfk_link_record: property " + std::to_string(p) + " is one of nfk_set_scene_props' properties");
+        mine[p >> 6] |= 1ull << (p & 63);
+    }
+    // (checked before anything is changed; a link without a linked column is no link)
+    memset(w->lk_pid[rec], 0xFF, sizeof(w->lk_pid[rec]));
+    w->lk_rows[rec] = (mine[0] | mine[1]) ? (int8_t)rows : (int8_t)0;
+    for (int c = 0; w->lk_rows[rec] && c < cols; c++) w->lk_pid[rec][c] = (int8_t)col_pid[c];
+    link_pid_mask(w, -1, w->lk_pids);
     return NFK_OK;
 }
 
@@ -2119,6 +2186,32 @@ int nfk_commit(void* world) {
                 const int r = check_guard_cell(w, w->tab.ops[k][i]);
                 if (r) return r;
             }
+    // property links against the records' final shapes, and against the programs: a linked property
+    // belongs to its link (no program writes it), and no record op feeds a linked column
+    for (int r = 0; r < NR; r++) {
+        if (!w->lk_rows[r]) continue;
+        if (w->lk_rows[r] > w->tab.rec_rows[r])
+            return fail(NFK_ERR_ARG, "record " + std::to_string(r) + " was redefined with fewer rows than its link sums");
+        for (int c = 0; c < NFK_MAX_REC_COLS; c++)
+            if (w->lk_pid[r][c] >= 0 && (c >= w->tab.rec_cols[r] || w->rec_ctype[r][c] != NFK_REC_INT))
+                return fail(NFK_ERR_ARG, "record " + std::to_string(r) + " was redefined: linked column " + std::to_string(c) +
+                                             " is not an int column");
+    }
+    if (w->lk_pids[0] | w->lk_pids[1]) {
+        if (w->linked_pid(w->pid_scene) || w->linked_pid(w->pid_group))
+            return fail(NFK_ERR_ARG, "a linked property is one of nfk_set_scene_props' properties");
+        for (int k = 0; k < NK; k++)
+            for (int i = 0; i < w->tab.nops[k]; i++) {
+                const nfk_op& op = w->tab.ops[k][i];
+                if (op.code == NFK_OP_RIADD_CLAMP || op.code == NFK_OP_RFAFFINE) {
+                    const int r = op.dst >> 8, c = op.dst & 255;  // (in range: nfk_define_kind)
+                    if (r < NR && c < NFK_MAX_REC_COLS && w->lk_rows[r] && w->lk_pid[r][c] >= 0)
+                        return fail(NFK_ERR_ARG, "kind " + std::to_string(k) + ": a record op targets a linked (record, column)");
+                } else if (prop_op(op.code) && w->linked_pid(op.dst)) {
+                    return fail(NFK_ERR_ARG, "kind " + std::to_string(k) + " writes linked property " + std::to_string(op.dst));
+                }
+            }
+    }
     // record ops: compiled list sorted by (rec, col); distinct (rec, col) required
     int nro = 0;
     for (int k = 0; k < NK; k++)
@@ -2424,6 +2517,9 @@ static int queue_sets(World* w, int32_t n, const int32_t* obj, const int32_t* pi
         if (pid[i] < 0 || pid[i] >= w->n_if)
             return fail(NFK_ERR_ARG, pid[i] >= w->n_if && pid[i] < w->n_prop ? "object property: use nfk_set_objects"
                                                                               : "bad property id");
+        if (w->linked_pid(pid[i]))  // (the batch queues nothing)
+            return fail(NFK_ERR_ARG, "property " + std::to_string(pid[i]) + " is linked to a record column (nfk_link_record): "
+                                     "its value is its link's");
     }
     const size_t at = w->xops.size();
     w->xops.resize(at + (size_t)n);
@@ -2452,6 +2548,11 @@ int nfk_set_props(void* world, int32_t n, const int64_t* gh, const int64_t* gd, 
     World* w = (World*)world;
     if (!w || n < 0 || (n && (!gh || !gd || !pid || !bits))) return fail(NFK_ERR_ARG, "null argument");
     if (!w->committed) return fail(NFK_ERR_STATE, "commit first");
+    if (w->lk_pids[0] | w->lk_pids[1])  // a direct Set of a linked property: refused, nothing queued
+        for (int32_t i = 0; i < n; i++)
+            if (w->linked_pid(pid[i]))
+                return fail(NFK_ERR_ARG, "property " + std::to_string(pid[i]) + " is linked to a record column (nfk_link_record): "
+                                         "its value is its link's");
     // a large batch in a world without object properties: looked up and queued on the device
     if (w->dev_look_min && (size_t)n >= w->dev_look_min && w->cfg.n_obj == 0) return set_props_dev(w, n, gh, gd, pid, bits);
     w->look.resize(n);  // one GUID lookup per call
@@ -2760,6 +2861,60 @@ static void replay_column(const World* w, int32_t o, int32_t r, int32_t col, uin
             u = (u & ~(1ull << xr)) | (((u >> xc) & 1) << xr) | (1ull << xc);
         }
     }
+}
+
+// The link of column col of record r (nfk_link_record) over this window's queued calls on (object
+// o, record r), as k_rrows takes it: the calls replayed in call order on the used mask u and the
+// column's int cells c[rows] in ROW order; every record event whose nCol names the column — an
+// accepted Set of one of its cells; with col 0 an AddRow, a Remove (before the row goes) and each step
+// of a ClearRecord; a Swap whose target row's index is col — takes the sum of the column over the
+// link's rows, each cell truncated to int32, unused rows 0.  True when an event named the column:
+// *sum is the last one's.
+static bool replay_link(const World* w, int32_t o, int32_t r, int32_t col, uint64_t u, uint64_t* c, uint32_t* sum) {
+    auto it = w->rq_index.find(((uint64_t)o << 3) | (uint32_t)r);
+    if (it == w->rq_index.end()) return false;
+    const int32_t rows = w->tab.rec_rows[r], rows_l = std::min<int32_t>(w->lk_rows[r], rows);
+    bool hit = false;
+    auto event = [&]() {
+        uint32_t s = 0;
+        for (int i = 0; i < rows_l; i++) s += ((u >> i) & 1) ? (uint32_t)c[i] : 0u;
+        *sum = s;
+        hit = true;
+    };
+    for (uint32_t k : it->second) {
+        const World::RSOp& x = w->rsq[k];
+        const int xr = (int)((x.rrc >> 8) & 0xFF), xc = (int)(x.rrc & 0xFF);
+        if (x.op == 0) {
+            if (xc != col || !((u >> xr) & 1) || c[xr] == x.bits) continue;  // RC:194, RC:209
+            c[xr] = x.bits;
+            event();
+        } else if (x.op == 1) {
+            int rr = xr;
+            if (xr == 0xFF) {
+                const uint64_t fr = ~u & rec_rowm(rows);
+                if (!fr) continue;
+                rr = __builtin_ctzll(fr);
+            }
+            u |= 1ull << rr;
+            c[rr] = x.aux == 0xFFFFFFFFu ? 0ull : w->rvals[(size_t)x.aux * NFK_MAX_REC_COLS + col];
+            if (col == 0) event();
+        } else if (x.op == 2) {
+            if (!((u >> xr) & 1)) continue;
+            if (col == 0) event();
+            u &= ~(1ull << xr);
+        } else if (x.op == 3) {
+            for (int q = rows - 1; q >= 0; q--)
+                if ((u >> q) & 1) {
+                    if (col == 0) event();
+                    u &= ~(1ull << q);
+                }
+        } else if ((u >> xr) & 1) {  // SwapRowInfo (the col field: the target row)
+            std::swap(c[xr], c[xc]);
+            u = (u & ~(1ull << xr)) | (((u >> xc) & 1) << xr) | (1ull << xc);
+            if (xc == col) event();
+        }
+    }
+    return hit;
 }
 
 // whether the window's queued calls on (object o, record r) hold a SwapRowInfo
@@ -3406,6 +3561,66 @@ static int current_props(World* w, int32_t n, const int32_t* obj, const int32_t*
         }
         bits[i] = v;
     }
+    // 3. a linked property (nfk_link_record) whose (object, record) has queued calls: the list
+    //    replayed on the device's used mask and the one column; the sum at the last event that names
+    //    the column stays (none: the stored value)
+    if (w->lk_pids[0] | w->lk_pids[1]) {
+        // (the device's used mask and the column are read once per window and (object, property): ucache / lcache)
+        struct LEnt { int32_t i, r, c; const uint64_t* cells; uint64_t um; bool have_um, have_col; };
+        std::vector<LEnt> ent;
+        std::vector<uint64_t> addr;
+        for (int32_t i = 0; i < n; i++) {
+            if (!w->linked_pid(pid[i])) continue;
+            const int r = w->lk_of_pid[pid[i]] >> 4, c = w->lk_of_pid[pid[i]] & 15;
+            if (w->rq_index.find(((uint64_t)obj[i] << 3) | (uint32_t)r) == w->rq_index.end()) continue;
+            LEnt e{i, r, c, nullptr, 0, false, w->lcache.count(((uint64_t)obj[i] << 7) | (uint32_t)pid[i]) != 0};
+            auto it = w->ucache.find(((uint64_t)obj[i] << 3) | (uint32_t)r);
+            if (it != w->ucache.end()) {
+                e.um = it->second;
+                e.have_um = true;
+            }
+            const uint64_t* used;
+            if (int er = rec_addrs(w, obj[i], r, &e.cells, &used)) return er;
+            if (!e.have_um) addr.push_back((uint64_t)(uintptr_t)used);
+            ent.push_back(e);
+        }
+        if (!ent.empty()) {
+            std::vector<uint64_t> um(addr.size());
+            if (int e = read_abs(w, addr, um.data())) return e;
+            addr.clear();
+            size_t q = 0;
+            for (LEnt& e : ent) {
+                if (!e.have_um) {
+                    e.um = um[q++];
+                    w->ucache[((uint64_t)obj[e.i] << 3) | (uint32_t)e.r] = e.um;
+                }
+                const int rows = w->tab.rec_rows[e.r];
+                e.um &= rec_rowm(rows);
+                if (e.have_col) continue;
+                for (int p = 0, nu = __builtin_popcountll(e.um); p < nu; p++)  // (the used rows first: rec_pos)
+                    addr.push_back((uint64_t)(uintptr_t)(e.cells + (size_t)e.c * rows + p));
+            }
+            std::vector<uint64_t> cv(addr.size());
+            if (int e = read_abs(w, addr, cv.data())) return e;
+            size_t a = 0;
+            for (const LEnt& e : ent) {
+                const int rows = w->tab.rec_rows[e.r];
+                std::vector<uint64_t>& col = w->lcache[((uint64_t)obj[e.i] << 7) | (uint32_t)pid[e.i]];
+                if (col.empty()) {  // (two queries of one pair in this batch: the first fills it)
+                    col.assign(64, 0);
+                    if (!e.have_col)
+                        for (int row = 0; row < rows; row++)
+                            if ((e.um >> row) & 1) col[row] = cv[a++];
+                } else if (!e.have_col) {
+                    a += (size_t)__builtin_popcountll(e.um);
+                }
+                uint64_t c[64];
+                memcpy(c, col.data(), sizeof c);
+                uint32_t sum;
+                if (replay_link(w, obj[e.i], e.r, e.c, e.um, c, &sum)) bits[e.i] = (uint64_t)(int64_t)(int32_t)sum;
+            }
+        }
+    }
     return NFK_OK;
 }
 
@@ -3962,6 +4177,8 @@ int nfk_set_scene_props(void* world, int32_t pid_scene, int32_t pid_group, int32
     auto ok_f = [&](int32_t p) { return p == -1 || (p >= NI && p < w->n_if); };
     if (!ok_i(pid_scene) || !ok_i(pid_group) || !ok_f(pid_x) || !ok_f(pid_y) || !ok_f(pid_z))
         return fail(NFK_ERR_ARG, "SceneID/GroupID must be int properties, X/Y/Z float properties");
+    if (w->linked_pid(pid_scene) || w->linked_pid(pid_group))
+        return fail(NFK_ERR_ARG, "SceneID/GroupID must not be linked properties (nfk_link_record)");
     w->pid_scene = pid_scene;
     w->pid_group = pid_group;
     w->pid_x = pid_x;
@@ -4179,6 +4396,29 @@ static int execute_frame(World* w, int64_t now_ms, bool calls_only) {
     // test hook: a failure right after the window's membership changes (tests/test_gpu_parity.py)
     if (const char* inj = getenv("NFGPU_INJECT_EXEC_FAIL"); inj && inj[0] == '1')
         return drop_window(w, fail(NFK_ERR_CAPACITY, "injected failure after the membership changes"));
+    // property links: one placeholder SetProperty call per (object, linked property that a record
+    // call of the window can hit), so that the slot's group of that property exists for k_links
+    // (and the tile counts as one with SetProperty work).  An event names the cell's column (Set),
+    // column 0 (AddRow / Remove / ClearRecord) or the column whose index is a Swap's target row.
+    bool lk_on = false;
+    if ((w->lk_pids[0] | w->lk_pids[1]) && !w->rsq.empty())
+        for (const auto& kv : w->rq_index) {
+            const uint32_t rec = (uint32_t)(kv.first & 7), o = (uint32_t)(kv.first >> 3);
+            if (!w->lk_rows[rec] || w->slot_of_obj[o] < 0) continue;
+            lk_on = true;
+            uint32_t colm = 0;
+            for (uint32_t i : kv.second) {
+                const World::RSOp& x = w->rsq[i];
+                const uint32_t c = x.op == 0 ? (x.rrc & 0xFF) : x.op == 4 ? (x.rrc & 0xFF) : 0u;
+                if (c < NFK_MAX_REC_COLS) colm |= 1u << c;
+            }
+            for (; colm; colm &= colm - 1) {
+                const int pid = w->lk_pid[rec][__builtin_ctz(colm)];
+                if (pid < 0) continue;
+                w->xops.push_back(World::XOp{o, (uint32_t)pid, 0ull});
+                count_standalone(w, (uint32_t)pid);
+            }
+        }
     if (w->cfg.n_obj) w->xops_h.resize(w->xops.size(), 0);
     if (w->s_unfixed && !w->hops.empty()) fix_schedule_steps(w);
     Dev d = w->d;
@@ -4248,6 +4488,11 @@ static int execute_frame(World* w, int64_t now_ms, bool calls_only) {
                 const int32_t sl = w->slot_of_obj[w->rsq[i].obj];
                 if (sl >= 0) rowpairs.push_back(((uint64_t)(uint32_t)sl << 3) | (w->rsq[i].rrc >> 16));
                 any_swap = any_swap || (sl >= 0 && w->rsq[i].op == 4);
+            }
+        if (lk_on)  // a linked record's calls always form a list: one pair per (object, record), not per call
+            for (const auto& kv : w->rq_index) {
+                const int32_t sl = w->slot_of_obj[kv.first >> 3];
+                if (sl >= 0 && w->lk_rows[kv.first & 7]) rowpairs.push_back(((uint64_t)(uint32_t)sl << 3) | (kv.first & 7));
             }
         std::sort(rowpairs.begin(), rowpairs.end());
         rowpairs.erase(std::unique(rowpairs.begin(), rowpairs.end()), rowpairs.end());
@@ -4409,16 +4654,15 @@ static int execute_frame(World* w, int64_t now_ms, bool calls_only) {
                 n_rev += evb[q];
             }
             // the tile bound: per record tile, its groups plus its lists' row-event bounds
-            std::vector<std::pair<uint32_t, uint32_t>> per_tile;  // (record tile, events)
-            for (size_t g = 0; g < rs_slot.size(); g++) per_tile.push_back({rs_slot[g] / kRTile, 1u});
-            for (size_t q = 0; q < npair; q++) per_tile.push_back({rl_slot[q] / kRTile, evb[q]});
-            std::sort(per_tile.begin(), per_tile.end());
-            for (size_t a = 0; a < per_tile.size();) {
+            // (the groups and the lists are both in slot order: one merge, no sort of an entry per group)
+            for (size_t g = 0, q = 0; g < rs_slot.size() || q < npair;) {
+                const uint32_t tg = g < rs_slot.size() ? rs_slot[g] / kRTile : 0xFFFFFFFFu;
+                const uint32_t tq = q < npair ? rl_slot[q] / kRTile : 0xFFFFFFFFu;
+                const uint32_t tile = std::min(tg, tq);
                 int64_t t = 0;
-                size_t b = a;
-                for (; b < per_tile.size() && per_tile[b].first == per_tile[a].first; b++) t += per_tile[b].second;
+                for (; g < rs_slot.size() && rs_slot[g] / kRTile == tile; g++) t += 1;
+                for (; q < npair && rl_slot[q] / kRTile == tile; q++) t += evb[q];
                 max_rs_tile = std::max(max_rs_tile, t);
-                a = b;
             }
         } else {
             uint32_t cur_rt = 0xFFFFFFFFu;
@@ -4558,6 +4802,15 @@ static int execute_frame(World* w, int64_t now_ms, bool calls_only) {
         r = dev_reserve(w, &w->rl_buf, &w->rl_cap, align16(std::max<size_t>(ngr, 1)) + (nrl + n_rev + 1) * 4);
         if (r) return drop_window(w, r);
     }
+    LinkDev lkd{};  // (hit / sum null: this window has no call on a linked record)
+    if (lk_on && nrl) {
+        int r = dev_reserve(w, &w->lk_buf, &w->lk_cap, nrl * 4 * (1 + NFK_MAX_REC_COLS));
+        if (r) return drop_window(w, r);
+        memcpy(lkd.rows, w->lk_rows, sizeof(lkd.rows));
+        memcpy(lkd.pid, w->lk_pid, sizeof(lkd.pid));
+        lkd.hit = (uint32_t*)w->lk_buf;
+        lkd.sum = lkd.hit + nrl;
+    }
     if (total > 0 && (ng || nhq || nrss)) {
         int r = pin_reserve(w, total);
         if (r) return drop_window(w, r);
@@ -4652,6 +4905,7 @@ static int execute_frame(World* w, int64_t now_ms, bool calls_only) {
     w->rvals.clear();
     w->rq_index.clear();
     w->ucache.clear();
+    w->lcache.clear();
     w->xops.clear();
     w->xq_n = 0;
     w->xops_h.clear();
@@ -4687,7 +4941,8 @@ static int execute_frame(World* w, int64_t now_ms, bool calls_only) {
             if (ngr)
                 hipLaunchKernelGGL(k_rsets, dim3((unsigned)((ngr + kTPB - 1) / kTPB)), dim3(kTPB), 0, w->stream, d, rh);
             if (nrl)  // after k_rsets: it clears the has-flags of the lists' groups
-                hipLaunchKernelGGL(k_rrows, dim3((unsigned)((nrl + kTPB - 1) / kTPB)), dim3(kTPB), 0, w->stream, d, rh);
+                hipLaunchKernelGGL(lkd.hit ? k_rrows<true> : k_rrows<false>, dim3((unsigned)((nrl + kTPB - 1) / kTPB)), dim3(kTPB), 0,
+                                   w->stream, d, rh, lkd);
         }
         if (ng) {
             // the device fold: keys (slot << 7 | property) -> stable radix sort -> groups
@@ -4727,7 +4982,16 @@ static int execute_frame(World* w, int64_t now_ms, bool calls_only) {
                 w->xq_ev_set[b] = true;
                 w->xq_b ^= 1;
             }
-            hipLaunchKernelGGL(k_sets, dim3((unsigned)((ng + kTPB - 1) / kTPB)), dim3(kTPB), 0, w->stream, d);
+            if (lk_on) {  // the linked properties' groups keep their values; k_links gives them the window's sums
+                LinkPids lp{{w->lk_pids[0], w->lk_pids[1]}};
+                hipLaunchKernelGGL(k_sets<true>, dim3((unsigned)((ng + kTPB - 1) / kTPB)), dim3(kTPB), 0, w->stream, d, lp);
+                if (lkd.hit)
+                    hipLaunchKernelGGL(k_links, dim3((unsigned)((nrl * NFK_MAX_REC_COLS + kTPB - 1) / kTPB)), dim3(kTPB), 0,
+                                       w->stream, d, lkd);
+            } else {
+                hipLaunchKernelGGL(k_sets<false>, dim3((unsigned)((ng + kTPB - 1) / kTPB)), dim3(kTPB), 0, w->stream, d,
+                                   LinkPids{});
+            }
         }
         if (nhq) {
             // the device fold of the schedule calls: keys -> stable radix sort -> per-slot counts ->
@@ -5841,6 +6105,16 @@ int nfk_query_objects(void* world, int32_t n_q, const nfk_query* q, nfk_query_re
             const int32_t pid = (int32_t)(kv.first & 127), o = (int32_t)(kv.first >> 7);
             if (((pidmask[pid >> 6] >> (pid & 63)) & 1) && !w->m_flag[o]) xaff.push_back({pid, o});
         }
+        // a queried linked property (nfk_link_record): queued calls on its record count as a queued Set
+        if ((pidmask[0] & w->lk_pids[0]) | (pidmask[1] & w->lk_pids[1]))
+            for (const auto& kv : w->rq_index) {
+                const int32_t r = (int32_t)(kv.first & 7), o = (int32_t)(kv.first >> 3);
+                if (!w->lk_rows[r] || w->m_flag[o] || !w->alive[o]) continue;
+                for (int c = 0; c < NFK_MAX_REC_COLS; c++) {
+                    const int32_t pid = w->lk_pid[r][c];
+                    if (pid >= 0 && ((pidmask[pid >> 6] >> (pid & 63)) & 1)) xaff.push_back({pid, o});
+                }
+            }
         std::sort(xaff.begin(), xaff.end());
     }
     auto xaff_of = [&](int32_t pid) {

@@ -182,12 +182,24 @@ __global__ void k_xgroups(const uint64_t* __restrict__ keys, const uint32_t* __r
 // different properties never interact and every call precedes the frame's heartbeat scan, so the
 // groups are independent.  The column gets the value after the group; x_old / x_new keep the
 // frame-start value and that value for the frame's diff.
-__global__ __launch_bounds__(kTPB) void k_sets(Dev d) {
+// kLinks (a world with nfk_link_record links): a group of a LINKED property (bit pid of lk) holds
+// only the host's placeholder calls (a direct Set of one is refused); it keeps x_old = x_new = the
+// stored value and k_links, after k_rrows, gives it the window's last sum.
+struct LinkPids {
+    uint64_t m[2];
+};
+template <bool kLinks>
+__global__ __launch_bounds__(kTPB) void k_sets(Dev d, LinkPids lk) {
     const int g = blockIdx.x * kTPB + threadIdx.x;
     if (g >= d.n_x || d.x_slot[g] == kNoGroupSlot) return;
     const uint32_t pid = d.x_pid[g];
     uint64_t* p = prop_ptr(d, pid, (int)d.x_slot[g]);
     const uint64_t start = *p;
+    if (kLinks && ((lk.m[pid >> 6] >> (pid & 63)) & 1)) {
+        d.x_old[g] = start;
+        d.x_new[g] = start;
+        return;
+    }
     uint64_t cur = start;
     const uint32_t i1 = d.x_first[g + 1];
     if ((int)pid >= d.n_if) {
@@ -914,6 +926,19 @@ struct RecHeads {
     const uint32_t* rs_swap;
 };
 
+// Property links (nfk_link_record; NFCPropertyModule::OnRecordPropertyEvent, PM:127-149): after every
+// record event of a linked record the int property col_pid[nCol] takes the 32-bit sum of column nCol
+// over the record's first `rows` rows (GetInt: 0 for a row unused at that instant, RC:616-635).
+// A third argument of k_rrows and k_links' own, not part of Dev.  hit / sum are null in a window
+// without calls on a linked record, which launches k_rrows<false>.
+struct LinkDev {
+    int8_t rows[NFK_MAX_RECORDS];                    // rows summed (0: the record has no link)
+    int8_t pid[NFK_MAX_RECORDS][NFK_MAX_REC_COLS];   // the column's int property (-1: none)
+    uint32_t* hit;   // [n_rl] the linked columns an event of the list named
+    uint32_t* sum;   // [n_rl][NFK_MAX_REC_COLS] the sum at the column's last such event
+};
+static_assert(NFK_MAX_PROPS <= 128 && NFK_MAX_REC_ROWS <= 127, "LinkDev's int8 fields");
+
 __global__ __launch_bounds__(kTPB) void k_rsets(Dev d, RecHeads h) {
     const int g = blockIdx.x * kTPB + threadIdx.x;
     if (g >= d.n_rs) return;
@@ -1008,7 +1033,10 @@ __device__ void rec_repack(uint64_t* cells, int rows, int cols, uint64_t rowm, u
     }
 }
 
-__global__ __launch_bounds__(kTPB) void k_rrows(Dev d, RecHeads h) {
+// kLinks: a window with calls on a linked record (LinkDev); every other window launches
+// k_rrows<false>, in which the link code is compiled out.
+template <bool kLinks>
+__global__ __launch_bounds__(kTPB) void k_rrows(Dev d, RecHeads h, LinkDev lk) {
     const int l = blockIdx.x * kTPB + threadIdx.x;
     if (l >= d.n_rl) return;
     const uint32_t e = d.rl_slot[l];
@@ -1030,6 +1058,18 @@ __global__ __launch_bounds__(kTPB) void k_rrows(Dev d, RecHeads h) {
     rec_repack(cells, rows, cols, rowm, used, 0ull);
     uint32_t* ev = d.rl_ev + d.rl_ev0[l];
     unsigned nev = 0;
+    // a linked record: the record event that names column c (the event's nCol field) leaves the
+    // sum of c over the first rows_l rows, each cell truncated to int32 and the add modulo 2^32, with
+    // the used mask of that instant; the last event of a column stays (k_links stores it)
+    const int rows_l = kLinks ? min((int)lk.rows[r], rows) : 0;
+    uint32_t lhit = 0;
+    auto link_event = [&](uint32_t c) {
+        if (!kLinks || rows_l == 0 || c >= (uint32_t)cols || lk.pid[r][c] < 0) return;
+        uint32_t s = 0;
+        for (int i = 0; i < rows_l; i++) s += ((used >> i) & 1) ? (uint32_t)cells[(size_t)c * rows + i] : 0u;
+        lk.sum[(size_t)l * NFK_MAX_REC_COLS + c] = s;
+        lhit |= 1u << c;
+    };
     for (uint32_t k = d.rl_c0[l]; k < d.rl_c0[l + 1]; k++) {
         const uint32_t code = d.rc_code[k];
         const uint32_t op = code & 0xFF, row = (code >> 8) & 0xFF, col = (code >> 16) & 0xFF;
@@ -1068,6 +1108,7 @@ __global__ __launch_bounds__(kTPB) void k_rrows(Dev d, RecHeads h) {
             }
             d.rs_new[g] = x;
             *c = x;
+            link_event(col);  // Update: nCol the cell's column, after the store
         } else if (op == 1) {
             int rr = (int)row;
             bool cover = false;
@@ -1083,15 +1124,20 @@ __global__ __launch_bounds__(kTPB) void k_rrows(Dev d, RecHeads h) {
             for (int c = 0; c < cols; c++)
                 cells[(size_t)c * rows + rr] = vi == 0xFFFFFFFFu ? 0ull : d.rvals[(size_t)vi * NFK_MAX_REC_COLS + c];
             ev[nev++] = ((cover ? 3u : 1u) << 8) | (uint32_t)rr;
+            link_event(0);  // Add / Cover: nCol 0, the row written and used (RC:157-177)
         } else if (op == 2) {
             if (!((used >> row) & 1)) continue;
             ev[nev++] = (2u << 8) | row;
+            link_event(0);  // Del: nCol 0, before the used bit goes (RC:1098-1100)
             used &= ~(1ull << row);
         } else if (op == 4) {
             const uint32_t tgt = col;  // (the col field carries the target row)
             if (!((used >> row) & 1)) continue;  // RC:1221
             ev[nev++] = (4u << 8) | row | (tgt << 16);
-            if (tgt == row) continue;
+            if (tgt == row) {
+                link_event(tgt);
+                continue;
+            }
             for (int c = 0; c < cols; c++) {
                 uint64_t* v = cells + (size_t)c * rows;
                 const uint64_t t = v[row];
@@ -1121,10 +1167,12 @@ __global__ __launch_bounds__(kTPB) void k_rrows(Dev d, RecHeads h) {
                     h.rs_new_h[gb] = t;
                 }
             }
+            link_event(tgt);  // Swap: nCol the TARGET ROW's index, after the exchange (RC:1240-1247)
         } else {
             for (int q = rows - 1; q >= 0; q--)
                 if ((used >> q) & 1) {
                     ev[nev++] = (2u << 8) | (uint32_t)q;
+                    link_event(0);
                     used &= ~(1ull << q);
                 }
         }
@@ -1132,6 +1180,30 @@ __global__ __launch_bounds__(kTPB) void k_rrows(Dev d, RecHeads h) {
     rec_repack(cells, rows, cols, rowm, 0ull, used);
     usedp[e] = used;
     d.rl_cnt[l] = nev;
+    if (kLinks) lk.hit[l] = lhit;
+}
+
+// The links' SetPropertyInt (PM:146), one thread per (list, column) after k_rrows and k_sets: a column
+// an event of the list named stores its last sum, sign-extended from 32 bits, through the int
+// predicate (PR:254: only a different value) into the property's column and into x_new of the
+// slot's SetProperty group of that property — the host's placeholder call made the group, k_sets left
+// it at x_old = x_new = the stored value — so k_tick reports it as it reports a standalone queued Set.
+__global__ __launch_bounds__(kTPB) void k_links(Dev d, LinkDev lk) {
+    const int i = blockIdx.x * kTPB + threadIdx.x;
+    const int l = i / NFK_MAX_REC_COLS, c = i % NFK_MAX_REC_COLS;
+    if (l >= d.n_rl || !((lk.hit[l] >> c) & 1)) return;
+    const uint32_t e = d.rl_slot[l];
+    const uint32_t pid = (uint32_t)lk.pid[d.rl_rec[l]][c];
+    const uint32_t xh = d.ext_head[e];
+    if (!xh) return;
+    for (int g = (int)xh - 1; g < d.n_x && d.x_slot[g] == e; g++) {
+        if (d.x_pid[g] != pid) continue;
+        const uint64_t v = (uint64_t)(int64_t)(int32_t)lk.sum[(size_t)l * NFK_MAX_REC_COLS + c];
+        uint64_t* p = prop_ptr(d, pid, (int)e);
+        if (*p != v) *p = v;
+        d.x_new[g] = v;
+        return;
+    }
 }
 
 // The slots with SetRecord groups this window, one wave each (lane = row), every record of the

@@ -4,10 +4,13 @@
 #include <dlfcn.h>
 
 #include <algorithm>
+#include <atomic>
 #include <chrono>
 #include <cstdlib>
 #include <cstring>
+#include <mutex>
 #include <numeric>
+#include <unordered_map>
 
 namespace nfgpu {
 
@@ -27,7 +30,38 @@ NFGPUKernelModule::NFGPUKernelModule(int capacity, void* hip_stream)
 
 void NFGPUKernelModule::SetTimeSource(std::function<int64_t()> now_ms) { clock_ = now_ms ? now_ms : nf_get_time; }
 
+// LinkRecordColumns' state, kept beside the modules and not in them (the header's layout policy: programs
+// that hold a module by value run on a newer libnfgpu_plugin.so without being rebuilt).  One entry per
+// module that defined a link; while no module of the process has one, SetPropertyInt pays one atomic load.
+namespace {
+struct LinkDef {
+    std::string record;
+    int rows;
+    std::vector<std::string> props;  // per logical column, "" for none
+};
+struct LinkState {
+    std::vector<LinkDef> links;
+    std::vector<bool> linked;  // props_ index -> the property hangs on a record column (AfterInit)
+};
+std::mutex g_link_mu;
+std::unordered_map<const void*, LinkState> g_links;
+std::atomic<int> g_link_modules{0};
+
+void drop_links(const void* self) {
+    if (!g_link_modules.load(std::memory_order_acquire)) return;
+    std::lock_guard<std::mutex> lk(g_link_mu);
+    if (g_links.erase(self)) g_link_modules.fetch_sub(1, std::memory_order_release);
+}
+bool linked_property(const void* self, size_t p) {
+    if (!g_link_modules.load(std::memory_order_acquire)) return false;
+    std::lock_guard<std::mutex> lk(g_link_mu);
+    auto it = g_links.find(self);
+    return it != g_links.end() && p < it->second.linked.size() && it->second.linked[p];
+}
+}  // namespace
+
 NFGPUKernelModule::~NFGPUKernelModule() {
+    drop_links(this);
     WaitGather();
     pool_.reset();
     if (world_) nfk_destroy(world_);
@@ -84,6 +118,26 @@ void NFGPUKernelModule::SetRecordFlags(const std::string& cls, const std::string
                                        bool upload) {
     classes_.at(class_id_.at(cls)).record_flags[rec] =
         (pub ? NFK_PUBLIC : 0) | (priv ? NFK_PRIVATE : 0) | (upload ? NFK_UPLOAD : 0);
+}
+
+void NFGPUKernelModule::LinkRecordColumns(const std::string& strRecordName, int rows,
+                                          const std::vector<std::string>& propertyNames) {
+    if (committed_) throw std::runtime_error("LinkRecordColumns after AfterInit");
+    auto it = record_id_.find(strRecordName);
+    if (it == record_id_.end()) throw std::invalid_argument("LinkRecordColumns: no record " + strRecordName);
+    if (propertyNames.size() != records_[it->second].cols.size())
+        throw std::invalid_argument("LinkRecordColumns " + strRecordName + ": one property name (or \"\") per column");
+    // a Swap event names the column whose index is its target row: the device's physical column, the
+    // reference's logical one.  They are the same column only in a record without object columns.
+    for (TDATA_TYPE t : records_[it->second].cols)
+        if (t == TDATA_OBJECT)
+            throw std::invalid_argument("LinkRecordColumns " + strRecordName + ": a record with an object column cannot be linked");
+    for (const std::string& nm : propertyNames)
+        if (!nm.empty() && !prop_id_.count(nm)) throw std::invalid_argument("LinkRecordColumns: no property " + nm);
+    std::lock_guard<std::mutex> lk(g_link_mu);
+    auto ins = g_links.emplace(this, LinkState{});
+    if (ins.second) g_link_modules.fetch_add(1, std::memory_order_release);
+    ins.first->second.links.push_back({strRecordName, rows, propertyNames});
 }
 
 void NFGPUKernelModule::AddHeartBeatProgram(const std::string& name, const std::vector<nfk_op>& ops) {
@@ -300,6 +354,30 @@ bool NFGPUKernelModule::AfterInit() {
         }
         check(nfk_define_record(world_, r, records_[r].rows, records_[r].pcols, ct.data(), fl.data()),
               "nfk_define_record");
+    }
+    std::vector<LinkDef> links;
+    std::vector<bool> linked(props_.size(), false);
+    if (g_link_modules.load(std::memory_order_acquire)) {
+        std::lock_guard<std::mutex> lk(g_link_mu);
+        auto it = g_links.find(this);
+        if (it != g_links.end()) links = it->second.links;
+    }
+    for (const LinkDef& ld : links) {  // (the entry point is looked up: a library without it cannot link)
+        using Fn = int (*)(void*, int32_t, int32_t, const int32_t*, int32_t);
+        Fn fn = (Fn)nfgpu_symbol("nfk_link_record");
+        if (!fn) throw std::runtime_error("nfk_link_record: the nfgpu library has no such entry point");
+        const RecordDef& rd = records_[record_id_.at(ld.record)];
+        std::vector<int32_t> col_pid((size_t)rd.pcols, -1);
+        for (size_t c = 0; c < ld.props.size(); c++) {
+            if (ld.props[c].empty()) continue;
+            col_pid[(size_t)rd.phys[c]] = PropertyId(ld.props[c]);
+            linked[(size_t)prop_id_.at(ld.props[c])] = true;
+        }
+        check(fn(world_, record_id_.at(ld.record), ld.rows, col_pid.data(), NFK_LINK_SUM32), "nfk_link_record");
+    }
+    if (!links.empty()) {
+        std::lock_guard<std::mutex> lk(g_link_mu);
+        g_links[this].linked = linked;
     }
     // schedule names -> kind ids in lexical order (NFMapEx<std::string, NFCScheduleElement> order)
     std::sort(heartbeats_.begin(), heartbeats_.end(),
@@ -719,6 +797,7 @@ int NFGPUKernelModule::ObjectIndex(const NFGUID& g) const { return obj_of_.find(
 bool NFGPUKernelModule::SetPropertyInt(const NFGUID& self, const std::string& name, int64_t v) {
     const int p = prop_ix_.find(name);
     if (!committed_ || p < 0 || props_[(size_t)p].type != TDATA_INT) return false;
+    if (linked_property(this, (size_t)p)) return false;  // (a linked property's value is its link's: LinkRecordColumns)
     if (walk_reads_ && in_walk_) WalkWrote(self, dev_pid_[(size_t)p]);
     qs_h_.push_back(self.nHead64);
     qs_d_.push_back(self.nData64);

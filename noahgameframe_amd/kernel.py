@@ -83,6 +83,7 @@ VIEW_PUBLIC, VIEW_PRIVATE = 1, 2
 REC_INT, REC_F64, REC_OBJ_DATA, REC_OBJ_HEAD = 0, 1, 2, 3
 REC_OBJECT = (REC_OBJ_DATA, REC_OBJ_HEAD)   # col_types.extend(REC_OBJECT): one logical object column
 MAX_RECORDS = 8   # NFK_MAX_RECORDS
+LINK_SUM32 = 0    # NFK_LINK_SUM32 (nfk_link_record's mode)
 Q_PLAYERS, Q_OTHERS = 0, 1
 Q_ALL_GROUPS = 1
 Q_INT_EQ32, Q_OBJ_EQ = 0, 1
@@ -153,6 +154,7 @@ def load_library(path=LIB_PATH):
         "nfk_find_objects": [VP, I32, VP, VP, VP, VP, VP, VP, VP],
         "nfk_find_objects_obj": [VP, I32, VP, VP, VP, VP, VP, VP], "nfk_read_rec_events_obj": [VP, VP, VP],
         "nfk_swap_rows": [VP, I32, VP, VP, VP, VP, VP],
+        "nfk_link_record": [VP, I32, I32, VP, I32],
     }
     for name, args in sig.items():
         if not hasattr(lib, name) and os.environ.get("NFGPU_LIB"):
@@ -254,6 +256,17 @@ class NFKernelModule:
         c = np.ascontiguousarray(cells, np.uint64)
         u = np.ascontiguousarray(used, np.uint64)
         self._chk(self.lib.nfk_load_record(self.h, rec, _p(c), _p(u)))
+
+    # ---- NFCPropertyModule::OnRecordPropertyEvent (PM:127-149) as part of the schema ----
+    def link_record(self, rec, rows, col_pid):
+        """nfk_link_record, before commit: after every record event of `rec` the int property
+        col_pid[nCol] takes the 32-bit sum of column nCol over the record's first `rows` rows
+        (nCol: a Set's column; 0 for AddRow / Remove / ClearRecord; a Swap's target row).
+        col_pid: one property id per column, -1 for none; None removes the record's link."""
+        cp = None if col_pid is None else np.ascontiguousarray(col_pid, np.int32)
+        if cp is not None and len(cp) != self.rec_shape.get(rec, (len(cp), 0))[0]:
+            raise ValueError("link_record: one property id (or -1) per column of the record")
+        self._chk(self.lib.nfk_link_record(self.h, rec, rows, None if cp is None else _p(cp), LINK_SUM32))
 
     def commit(self):
         self._chk(self.lib.nfk_commit(self.h))
