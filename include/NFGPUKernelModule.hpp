@@ -533,6 +533,17 @@ public:
                      float fOrient = 0.0f, const std::vector<TData>& arg = {});
     // NFCKernelModule::DestroyObject (KM:273-308): leaves its group, its schedules go with it
     bool DestroyObject(const NFGUID& self);
+    // NFISceneAOIModule::AddObjectEnterCallBack / AddObjectLeaveCallBack: cb(to, about) is what
+    // OnObjectListEnter / OnObjectListLeave hand out (AOI:651-675).  With either registered, Execute()
+    // flushes the buffered calls, asks the world once for the window's view changes (nfk_view_changes)
+    // before the device frame and replays, per membership call of the window in call order, the calls
+    // NFCSceneAOIModule::OnGroupEvent / OnSceneEvent / OnClassCommonEvent (AOI:292-529) make inside
+    // SwitchScene, CreateObject and DestroyObject, with the group lists as they stood at that call.
+    // With a shard attached a departure is delivered as the leaving half of a cross-scene switch and an
+    // arrival as a CreateObject.  (The callbacks live beside the module: the layout policy above.)
+    using OBJECT_LIST_FUNCTOR = std::function<int(const std::vector<NFGUID>& to, const std::vector<NFGUID>& about)>;
+    bool AddObjectEnterCallBack(const OBJECT_LIST_FUNCTOR& cb);
+    bool AddObjectLeaveCallBack(const OBJECT_LIST_FUNCTOR& cb);
     bool RegisterCommonPropertyEvent(const PROPERTY_EVENT_FUNCTOR& cb);
     bool RegisterCommonRecordEvent(const RECORD_EVENT_FUNCTOR& cb);
 
@@ -849,6 +860,7 @@ private:
     void DropDeferred(const NFGUID& self);
     void Depart(int o, const NFGUID& self, int scene, int group, float x, float y, float z);
     void WindowApplied();
+    void DeliverViewChanges();  // before a device pass applies the window's membership
     std::function<int64_t()> clock_;
     nfk_summary summary_{};
     FrameStats stats_{};

@@ -634,6 +634,67 @@ int nfk_query_objects(void* world, int32_t n_q, const nfk_query* q, nfk_query_re
  * bookkeeping corrected by the window's membership calls — no launch, no device read */
 int nfk_online_count(void* world, int32_t scene, int32_t group, int32_t* n);
 
+/* ---- view changes: the group lists NFCSceneAOIModule::OnGroupEvent / OnSceneEvent /
+ * OnClassCommonEvent (AOI:292-529) read inside every SwitchScene, CreateObject and DestroyObject, each
+ * as of ITS call.  The window is everything queued since the last nfk_execute / nfk_execute_calls.
+ * nfk_switch_scene, nfk_destroy_objects, nfk_spawn_objects, nfk_import_objects and nfk_export_objects
+ * append one log entry per object whose (scene, group) or existence changes, in call order (a batch call
+ * in array order; a switch that changes neither scene nor group logs nothing); the log is cleared where
+ * the window's membership is applied.  Entry i expands to 0-4 visits (why, scene, group), the groups the
+ * reference reads, in its order:
+ *   NFK_VC_SWITCH inside a scene (KM:943):  GROUP_LEAVE (s, g0) if g0 > 0, GROUP_ENTER (s, g1) if g1 > 0
+ *   NFK_VC_SWITCH s0 -> s1 (KM:932-943):    GROUP_LEAVE (s0, g0) if g0 > 0, SCENE_LEAVE (s0, 0),
+ *                                           SCENE_ENTER (s1, 0), GROUP_ENTER (s1, g1) if g1 > 0
+ *   NFK_VC_DESTROY:                         DESTROY (s, g) when s > 0 (AOI:294-327)
+ *   NFK_VC_CREATE (spawn / import):         SCENE_ENTER (s, 0) when s != 0, GROUP_ENTER (s, g) if g > 0
+ *   NFK_VC_EXPORT:                          GROUP_LEAVE (s0, g0) if g0 > 0, SCENE_LEAVE (s0, 0)
+ * A visit answers two lists of object indices, the group's players and its other objects, each in
+ * NFGUID order (GetGroupObjectList's "players then others", KM:1169-1199), both without entry i's own
+ * object, as the group stood at instant i: the frame-start membership with entries 0 .. i-1 applied.  A
+ * switching or destroyed object is out of its old group at its own instant and not yet in its new one
+ * (KM:929 precedes 945, KM:291 precedes 294); a created one is in its group (KM:146) and skipped as
+ * self.  Player / other follows the class, as nfk_query_objects documents.  A group nobody has been in
+ * gives two empty lists.
+ * The result is owned by the world, in pinned host memory, valid until the next nfk_view_changes /
+ * nfk_execute / nfk_execute_calls.  Calling it twice in a window gives the same answer plus whatever
+ * was queued in between.  It waits for the world's stream, queues nothing and changes nothing a frame
+ * reads.  A visit whose group has more than NFK_VC_STINT_CAP membership intervals begun in the window
+ * is answered on the host (n_host counts them).  NFK_ERR_STATE before nfk_commit; NFK_ERR_CAPACITY when
+ * the BOUND of the window's list entries (per visit: the members of its group's segment plus the
+ * group's intervals of the window) exceeds NFK_VC_MAX_ENTRIES. */
+#define NFK_VC_SWITCH 0
+#define NFK_VC_DESTROY 1
+#define NFK_VC_CREATE 2
+#define NFK_VC_EXPORT 3
+#define NFK_VC_GROUP_LEAVE 0
+#define NFK_VC_GROUP_ENTER 1
+#define NFK_VC_SCENE_LEAVE 2
+#define NFK_VC_SCENE_ENTER 3
+#define NFK_VC_WHY_DESTROY 4
+#define NFK_VC_STINT_CAP 256           /* a group's intervals of one window merged on the device */
+#define NFK_VC_MAX_ENTRIES (1 << 24)   /* bound of one window's list entries (64 MiB read back) */
+typedef struct nfk_vc_entry {
+    int32_t obj, kind; /* object index (as ev_obj), NFK_VC_SWITCH / DESTROY / CREATE / EXPORT */
+    int32_t from_scene, from_group, to_scene, to_group; /* (CREATE: from = 0, 0; DESTROY / EXPORT: to = 0, 0) */
+} nfk_vc_entry; /* 24 bytes */
+typedef struct nfk_vc_visit {
+    int32_t why, scene, group; /* NFK_VC_GROUP_LEAVE ... NFK_VC_WHY_DESTROY */
+} nfk_vc_visit; /* 12 bytes */
+typedef struct nfk_view_changes_result {
+    int32_t n_calls, n_visits;
+    const nfk_vc_entry* log;     /* [n_calls] */
+    const uint32_t* call_visit;  /* [n_calls + 1]: entry i's visits are [call_visit[i], call_visit[i + 1]) */
+    const nfk_vc_visit* visit;   /* [n_visits] */
+    const uint32_t* visit_off;   /* [2 * n_visits + 1]: players of visit v at obj[off[2v], off[2v + 1]),
+                                    others at obj[off[2v + 1], off[2v + 2]) */
+    const int32_t* obj;          /* [visit_off[2 * n_visits]] */
+    double kernel_ms;            /* the launches' device time in ms (0 unless nfk_set_profiling is on) */
+    int64_t bytes;               /* read back from the device */
+    int32_t n_host;              /* visits answered on the host (groups past NFK_VC_STINT_CAP) */
+    int32_t n_tiles;             /* 256-slot tiles of the device batch */
+} nfk_view_changes_result;
+int nfk_view_changes(void* world, nfk_view_changes_result* out);
+
 /* ---- record finds: NFCRecord::FindInt / FindFloat / FindRowByColValue (RC:778-910) ----
  * n (object, record, column, argument) finds answered in one call: masks[i] has bit r set when row
  * r of the record is used and its cell in column col[i] equals bits[i] under the column's type —

@@ -343,6 +343,21 @@ struct World {
     std::unordered_set<uint64_t> known_groups;
     std::unordered_set<int32_t> known_scenes;
     hipEvent_t q_ev[2] = {nullptr, nullptr};
+    // view changes (nfk_view_changes): the window's membership log (appended by the membership calls,
+    // cleared where the window's membership is applied), the resident per-slot departure instants
+    // (all 0xFFFFFFFF between calls: a call scatters the window's leavers and restores them with the
+    // same list; vc_dirty: a failed call left some behind), the batch's device scratch and the pinned
+    // buffer of the upload and the result, both grown on demand; vc_last[object]: its open stint
+    std::vector<nfk_vc_entry> vc_log;
+    uint32_t* vc_tout = nullptr;
+    int32_t vc_tout_cap = 0;
+    bool vc_dirty = false;
+    void* vc_dev = nullptr;
+    size_t vc_dcap = 0;
+    char* vc_pin = nullptr;
+    size_t vc_pcap = 0;
+    std::vector<int32_t> vc_last;
+    hipEvent_t vc_ev[2] = {nullptr, nullptr};
     // record finds (nfk_find_rows): the batch's descriptors and row masks on the device and in
     // pinned host memory (descriptors first, masks behind them), both grown on demand; the last
     // call's figures for nfk_find_stats
@@ -1769,6 +1784,7 @@ int commit_membership(World* w, MemPlan& p) {
         w->src_row[o] = -1;
     }
     w->touched.clear();
+    w->vc_log.clear();
     w->ins_n = 0;
     const auto t_end = clk::now();
     auto ms = [](clk::time_point a, clk::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
@@ -1917,6 +1933,11 @@ int nfk_destroy(void* world) {
     if (w->chain_pin) (void)hipHostFree(w->chain_pin);
     if (w->q_dev) (void)hipFree(w->q_dev);
     if (w->q_pin) (void)hipHostFree(w->q_pin);
+    if (w->vc_tout) (void)hipFree(w->vc_tout);
+    if (w->vc_dev) (void)hipFree(w->vc_dev);
+    if (w->vc_pin) (void)hipHostFree(w->vc_pin);
+    for (auto e : w->vc_ev)
+        if (e) (void)hipEventDestroy(e);
     if (w->f_dev) (void)hipFree(w->f_dev);
     if (w->f_pin) (void)hipHostFree(w->f_pin);
     for (auto e : w->f_ev)
@@ -4217,6 +4238,7 @@ int nfk_switch_scene(void* world, int64_t gh, int64_t gd, int32_t scene, int32_t
     put(w->pid_group, (uint64_t)(int64_t)group);
     // RemoveObjectFromGroup + AddObjectToGroup (KM:928, 944): a new slot in the target group
     if (scene != w->scene[o] || group != w->group[o]) {
+        w->vc_log.push_back({o, NFK_VC_SWITCH, w->scene[o], w->group[o], scene, group});
         w->scene[o] = scene;
         w->group[o] = group;
         touch(w, o);
@@ -4237,6 +4259,7 @@ int nfk_destroy_objects(void* world, int32_t n, const int64_t* gh, const int64_t
         const int32_t o = w->obj_of.find(gh[i], gd[i]);
         w->obj_of.erase(gh[i], gd[i]);
         w->alive[o] = 0;
+        w->vc_log.push_back({o, NFK_VC_DESTROY, w->scene[o], w->group[o], 0, 0});
         touch(w, o);
     }
     return NFK_OK;
@@ -4299,6 +4322,7 @@ int nfk_export_objects(void* world, int32_t n, const int64_t* gh, const int64_t*
     for (int32_t i = 0; i < n; i++) {
         w->obj_of.erase(gh[i], gd[i]);
         w->alive[objs[i]] = 0;
+        w->vc_log.push_back({objs[i], NFK_VC_EXPORT, w->scene[objs[i]], w->group[objs[i]], 0, 0});
         touch(w, objs[i]);
     }
     if (getenv("NFGPU_TRACE_MEMBERSHIP")) {
@@ -4340,6 +4364,7 @@ static int import_common(World* w, int32_t n, const int64_t* gh, const int64_t* 
     for (int32_t i = 0; i < n; i++) {
         const int32_t o = add_object(w, gh[i], gd[i], scene[i], group[i], cls[i], isplayer[i]);
         w->src_row[o] = (int64_t)(w->ins_n + i);
+        w->vc_log.push_back({o, NFK_VC_CREATE, 0, 0, scene[i], group[i]});
         touch(w, o);
     }
     w->ins_n += n;
@@ -6348,6 +6373,320 @@ int nfk_online_count(void* world, int32_t scene, int32_t group, int32_t* n) {
         if (w->alive[o] && (scene < 0 || (w->scene[o] == scene && (group < 0 || w->group[o] == group)))) c++;
     }
     *n = (int32_t)c;
+    return NFK_OK;
+}
+
+// ---- view changes (nfk_view_changes) ----
+// entry i's visits in the reference's order (AOI:292-529 under KM:929-945, 248-249, 291-294)
+static void vc_visits(const nfk_vc_entry& e, std::vector<nfk_vc_visit>& out) {
+    const int32_t s0 = e.from_scene, g0 = e.from_group, s1 = e.to_scene, g1 = e.to_group;
+    switch (e.kind) {
+    case NFK_VC_SWITCH:
+        if (g0 > 0) out.push_back({NFK_VC_GROUP_LEAVE, s0, g0});
+        if (s0 != s1) {
+            out.push_back({NFK_VC_SCENE_LEAVE, s0, 0});
+            out.push_back({NFK_VC_SCENE_ENTER, s1, 0});
+        }
+        if (g1 > 0) out.push_back({NFK_VC_GROUP_ENTER, s1, g1});
+        break;
+    case NFK_VC_DESTROY:
+        if (s0 > 0) out.push_back({NFK_VC_WHY_DESTROY, s0, g0});
+        break;
+    case NFK_VC_CREATE:
+        if (s1 != 0) out.push_back({NFK_VC_SCENE_ENTER, s1, 0});
+        if (g1 > 0) out.push_back({NFK_VC_GROUP_ENTER, s1, g1});
+        break;
+    default:  // NFK_VC_EXPORT
+        if (g0 > 0) out.push_back({NFK_VC_GROUP_LEAVE, s0, g0});
+        out.push_back({NFK_VC_SCENE_LEAVE, s0, 0});
+        break;
+    }
+}
+
+int nfk_view_changes(void* world, nfk_view_changes_result* out) {
+    World* w = (World*)world;
+    if (!w || !out) return fail(NFK_ERR_ARG, "null argument");
+    if (!w->committed) return fail(NFK_ERR_STATE, "commit first");
+    *out = nfk_view_changes_result{};
+    static const uint32_t kNoOff[1] = {0};
+    out->call_visit = out->visit_off = kNoOff;
+    const size_t n = w->vc_log.size();
+    if (n == 0) {
+        HIPCHK(hipStreamSynchronize(w->stream));
+        return NFK_OK;
+    }
+    constexpr uint32_t kNever = 0xFFFFFFFFu;
+    std::vector<nfk_vc_visit> vis;
+    std::vector<uint32_t> cv(n + 1);
+    // the window's leavers (a frame-start member's first entry) and stints (every membership
+    // interval that begins in the window)
+    struct Stint { uint64_t key; int32_t obj, pos; uint32_t t_in, t_out; };
+    std::vector<Stint> st;
+    std::vector<int32_t> lv_slot;
+    std::vector<uint32_t> lv_val;
+    if (w->vc_last.size() < (size_t)w->n_obj) w->vc_last.resize(w->n_obj, -2);  // -2: no entry yet
+    auto resident = [w](int32_t o) { return w->slot_of_obj[o] >= 0 && w->src_row[o] < 0; };
+    for (size_t i = 0; i < n; i++) {
+        const nfk_vc_entry& e = w->vc_log[i];
+        cv[i] = (uint32_t)vis.size();
+        vc_visits(e, vis);
+        int32_t& last = w->vc_last[e.obj];
+        if (last == -2) {
+            if (e.kind != NFK_VC_CREATE && resident(e.obj)) {
+                lv_slot.push_back(w->slot_of_obj[e.obj]);
+                lv_val.push_back((uint32_t)i);
+            }
+        } else if (last >= 0) {
+            st[last].t_out = (uint32_t)i;
+        }
+        last = -1;
+        if (e.kind == NFK_VC_SWITCH || e.kind == NFK_VC_CREATE) {
+            last = (int32_t)st.size();
+            st.push_back({seg_key_of(e.to_scene, e.to_group), e.obj, 0, (uint32_t)i, kNever});
+        }
+    }
+    cv[n] = (uint32_t)vis.size();
+    for (size_t i = 0; i < n; i++) w->vc_last[w->vc_log[i].obj] = -2;
+    std::sort(st.begin(), st.end(), [w](const Stint& a, const Stint& b) {
+        if (a.key != b.key) return a.key < b.key;
+        if (guid_less(w, a.obj, b.obj)) return true;
+        if (guid_less(w, b.obj, a.obj)) return false;
+        return a.t_in < b.t_in;
+    });
+    for (size_t a = 0; a < st.size();) {  // pos: the lower-bound slot in the group's frame-start segment
+        size_t b = a;
+        while (b < st.size() && st[b].key == st[a].key) b++;
+        const auto it = std::lower_bound(w->seg_key.begin(), w->seg_key.end(), st[a].key);
+        if (it != w->seg_key.end() && *it == st[a].key) {
+            const World::Seg& sg = w->segs[it - w->seg_key.begin()];
+            for (size_t j = a; j < b; j++) {
+                const World::Guid k = w->guid[st[j].obj];
+                const auto at = std::lower_bound(sg.keys.begin(), sg.keys.end(), k, [](const World::Guid& x, const World::Guid& y) {
+                    return x.h != y.h ? x.h < y.h : x.d < y.d;
+                });
+                st[j].pos = sg.base + (int32_t)(at - sg.keys.begin());
+            }
+        }
+        a = b;
+    }
+    const size_t n_v = vis.size(), n_st = st.size(), n_lv = lv_slot.size();
+
+    // per visit: its slot range, its stints, its tiles and the bound of its two lists
+    struct Plan { int32_t seg, lo, hi, st0, st_n, tiles; bool host; };
+    std::vector<Plan> pl(n_v);
+    size_t nt = 0, ub = 0, ub_host = 0, n_host = 0;
+    int32_t max_tiles = 0;
+    for (size_t i = 0; i < n; i++)
+        for (uint32_t v = cv[i]; v < cv[i + 1]; v++) {
+            Plan& p = pl[v];
+            p.seg = find_seg(w, vis[v].scene, vis[v].group);
+            p.lo = p.hi = 0;
+            if (p.seg >= 0) {
+                p.lo = w->segs[p.seg].base;
+                p.hi = p.lo + (int32_t)w->segs[p.seg].objs.size();
+                if (p.lo < 0 || p.hi > w->d.cap) return fail(NFK_ERR_STATE, "segment table out of the slot range");
+            }
+            const uint64_t key = seg_key_of(vis[v].scene, vis[v].group);
+            const auto a = std::lower_bound(st.begin(), st.end(), key, [](const Stint& x, uint64_t k) { return x.key < k; });
+            const auto b = std::upper_bound(a, st.end(), key, [](uint64_t k, const Stint& x) { return k < x.key; });
+            p.st0 = (int32_t)(a - st.begin());
+            p.st_n = (int32_t)(b - a);
+            p.host = p.st_n > NFK_VC_STINT_CAP;
+            const size_t bound = (size_t)(p.hi - p.lo) + (size_t)p.st_n;
+            if (p.host) {
+                p.tiles = 0;
+                ub_host += bound;
+                n_host++;
+            } else {
+                // (a visit with stints has the tile of `hi`: a stint's pos lies in [lo, hi])
+                p.tiles = p.st_n ? (p.hi - p.lo) / kTile + 1 : (p.hi - p.lo + kTile - 1) / kTile;
+                ub += bound;
+            }
+            max_tiles = std::max(max_tiles, p.tiles);
+            nt += (size_t)p.tiles;
+        }
+    if (ub + ub_host > (size_t)NFK_VC_MAX_ENTRIES)
+        return fail(NFK_ERR_CAPACITY, "view changes: the window's lists can hold " + std::to_string(ub + ub_host) +
+                                          " entries, more than NFK_VC_MAX_ENTRIES (execute the window in parts)");
+
+    // one region uploaded (visits, the lists' first tiles, stints, leavers), one read back (offsets, lists)
+    const size_t nv2 = 2 * n_v + 1;
+    const size_t u_v = 0, u_t0 = align16(n_v * sizeof(VDev)), u_st = align16(u_t0 + nv2 * 4);
+    const size_t u_ls = align16(u_st + n_st * sizeof(VStint)), u_lv = align16(u_ls + n_lv * 4), u_end = align16(u_lv + n_lv * 4);
+    const size_t d_cnt = u_end, d_base = align16(d_cnt + 2 * nt * 4), d_off = align16(d_base + (2 * nt + 1) * 4);
+    const size_t r_obj = align16(nv2 * 4), r_bytes = r_obj + ub * 4;
+    const size_t d_end = d_off + r_bytes;
+    const size_t h_log = u_end, h_cv = align16(h_log + n * sizeof(nfk_vc_entry)), h_vis = align16(h_cv + (n + 1) * 4);
+    const size_t h_res = align16(h_vis + n_v * sizeof(nfk_vc_visit)), h_foff = align16(h_res + r_bytes);
+    const size_t h_fobj = align16(h_foff + nv2 * 4), h_end = h_fobj + (n_host ? (ub + ub_host) * 4 : 0);
+    if (int r = dev_reserve(w, &w->vc_dev, &w->vc_dcap, d_end)) return r;
+    if (h_end > w->vc_pcap) {
+        if (w->vc_pin) HIPCHK(hipHostFree(w->vc_pin));
+        w->vc_pin = nullptr;
+        const size_t c = std::max(h_end, w->vc_pcap + w->vc_pcap / 2);
+        w->vc_pcap = 0;  // (until the new buffer exists)
+        HIPCHK(hipHostMalloc((void**)&w->vc_pin, c, hipHostMallocDefault));
+        w->vc_pcap = c;
+    }
+    char* H = w->vc_pin;
+    char* D = (char*)w->vc_dev;
+    VDev* hv = (VDev*)(H + u_v);
+    int32_t* ht0 = (int32_t*)(H + u_t0);
+    VStint* hs = (VStint*)(H + u_st);
+    int32_t t0 = 0;
+    for (size_t i = 0; i < n; i++) {
+        const int32_t self = w->vc_log[i].obj;
+        for (uint32_t v = cv[i]; v < cv[i + 1]; v++) {
+            const Plan& p = pl[v];
+            VDev x{};
+            x.lo = p.lo;
+            x.hi = p.host ? p.lo : p.hi;
+            x.tile0 = t0;
+            x.tiles = p.tiles;
+            x.t = (uint32_t)i;
+            x.skip_slot = resident(self) ? w->slot_of_obj[self] : -1;
+            x.st0 = p.st0;
+            x.st_n = p.host ? 0 : p.st_n;
+            hv[v] = x;
+            ht0[2 * v] = 2 * t0;
+            ht0[2 * v + 1] = 2 * t0 + p.tiles;
+            t0 += p.tiles;
+        }
+    }
+    ht0[2 * n_v] = 2 * t0;
+    for (size_t j = 0; j < n_st; j++)
+        hs[j] = VStint{(uint32_t)st[j].obj | (w->isplayer[st[j].obj] ? 0x80000000u : 0u), st[j].pos, st[j].t_in, st[j].t_out};
+    if (n_lv) {
+        memcpy(H + u_ls, lv_slot.data(), n_lv * 4);
+        memcpy(H + u_lv, lv_val.data(), n_lv * 4);
+    }
+    memcpy(H + h_log, w->vc_log.data(), n * sizeof(nfk_vc_entry));
+    memcpy(H + h_cv, cv.data(), (n + 1) * 4);
+    if (n_v) memcpy(H + h_vis, vis.data(), n_v * sizeof(nfk_vc_visit));
+    uint32_t* roff = (uint32_t*)(H + h_res);
+    int32_t* robj = (int32_t*)(H + h_res + r_obj);
+    if (nt == 0) {
+        memset(roff, 0, nv2 * 4);  // (no slot and no stint to look at: nothing is launched)
+        HIPCHK(hipStreamSynchronize(w->stream));
+    } else {
+        if (w->vc_tout_cap < w->d.cap) {
+            HIPCHK(hipStreamSynchronize(w->stream));
+            if (w->vc_tout) HIPCHK(hipFree(w->vc_tout));
+            w->vc_tout = nullptr;
+            w->vc_tout_cap = 0;
+            HIPCHK(hipMalloc((void**)&w->vc_tout, (size_t)w->d.cap * 4));
+            w->vc_tout_cap = w->d.cap;
+            w->vc_dirty = true;
+        }
+        if (w->vc_dirty) HIPCHK(hipMemsetAsync(w->vc_tout, 0xFF, (size_t)w->vc_tout_cap * 4, w->stream));
+        const bool timed = w->profiling;
+        if (timed)
+            for (auto& e : w->vc_ev)
+                if (!e) HIPCHK(hipEventCreate(&e));
+        HIPCHK(hipMemcpyAsync(D, H, u_end, hipMemcpyHostToDevice, w->stream));
+        if (timed) HIPCHK(hipEventRecord(w->vc_ev[0], w->stream));
+        w->vc_dirty = true;  // (until the restore below has run)
+        if (n_lv)
+            hipLaunchKernelGGL(k_view_scatter, dim3(grid_for(n_lv)), dim3(kTPB), 0, w->stream, (const int32_t*)(D + u_ls),
+                               (const uint32_t*)(D + u_lv), (int)n_lv, w->vc_tout, w->vc_tout_cap);
+        // (the grid's y is at most 65535: a longer batch goes in runs of visits)
+        auto launch = [&](bool write) {
+            for (size_t y0 = 0; y0 < n_v; y0 += 65535) {
+                const dim3 grid((unsigned)max_tiles, (unsigned)std::min<size_t>(65535, n_v - y0));
+                if (!write)
+                    hipLaunchKernelGGL(k_view<false>, grid, dim3(kTPB), 0, w->stream, (const VDev*)(D + u_v) + y0,
+                                       (const VStint*)(D + u_st), w->d.fan_desc, (const uint32_t*)w->vc_tout,
+                                       (const int32_t*)w->slot_obj_d, (uint32_t*)(D + d_cnt), (const uint32_t*)nullptr,
+                                       (int32_t*)nullptr, 0u);
+                else
+                    hipLaunchKernelGGL(k_view<true>, grid, dim3(kTPB), 0, w->stream, (const VDev*)(D + u_v) + y0,
+                                       (const VStint*)(D + u_st), w->d.fan_desc, (const uint32_t*)w->vc_tout,
+                                       (const int32_t*)w->slot_obj_d, (uint32_t*)nullptr, (const uint32_t*)(D + d_base),
+                                       (int32_t*)(D + d_off + r_obj), (uint32_t)ub);
+            }
+        };
+        launch(false);
+        hipLaunchKernelGGL(k_query_scan, dim3(1), dim3(1024), 0, w->stream, (const uint32_t*)(D + d_cnt),
+                           (uint32_t*)(D + d_base), (int)(2 * nt), (const int32_t*)(D + u_t0), (int)(2 * n_v),
+                           (uint32_t*)(D + d_off));
+        launch(true);
+        if (n_lv)
+            hipLaunchKernelGGL(k_view_scatter, dim3(grid_for(n_lv)), dim3(kTPB), 0, w->stream, (const int32_t*)(D + u_ls),
+                               (const uint32_t*)nullptr, (int)n_lv, w->vc_tout, w->vc_tout_cap);
+        HIPCHK(hipGetLastError());
+        if (timed) HIPCHK(hipEventRecord(w->vc_ev[1], w->stream));
+        HIPCHK(hipMemcpyAsync(H + h_res, D + d_off, r_bytes, hipMemcpyDeviceToHost, w->stream));
+        HIPCHK(hipStreamSynchronize(w->stream));
+        w->vc_dirty = false;
+        out->bytes = (int64_t)r_bytes;
+        if (timed) {
+            float ms = 0;
+            HIPCHK(hipEventElapsedTime(&ms, w->vc_ev[0], w->vc_ev[1]));
+            out->kernel_ms = ms;
+        }
+        if (roff[2 * n_v] > ub) return fail(NFK_ERR_DEVICE, "view changes: more list entries than members and stints");
+    }
+    out->n_calls = (int32_t)n;
+    out->n_visits = (int32_t)n_v;
+    out->log = (const nfk_vc_entry*)(H + h_log);
+    out->call_visit = (const uint32_t*)(H + h_cv);
+    out->visit = (const nfk_vc_visit*)(H + h_vis);
+    out->visit_off = roff;
+    out->obj = robj;
+    out->n_host = (int32_t)n_host;
+    out->n_tiles = (int32_t)nt;
+    if (!n_host) return NFK_OK;
+
+    // groups past the stint cap: the same merge on the host, spliced between the device's lists
+    std::unordered_map<int32_t, uint32_t> left;  // frame-start members that leave: object -> instant
+    for (size_t i = n; i-- > 0;) {
+        const nfk_vc_entry& e = w->vc_log[i];
+        if (e.kind != NFK_VC_CREATE && resident(e.obj)) left[e.obj] = (uint32_t)i;  // (the first entry wins)
+    }
+    uint32_t* foff = (uint32_t*)(H + h_foff);
+    int32_t* fobj = (int32_t*)(H + h_fobj);
+    uint32_t at = 0;
+    std::vector<int32_t> others;
+    for (size_t i = 0; i < n; i++) {
+        const uint32_t t = (uint32_t)i;
+        const int32_t self = w->vc_log[i].obj;
+        for (uint32_t v = cv[i]; v < cv[i + 1]; v++) {
+            const Plan& p = pl[v];
+            foff[2 * v] = at;
+            if (!p.host) {
+                const uint32_t a = roff[2 * v], m = roff[2 * v + 1], b = roff[2 * v + 2];
+                memcpy(fobj + at, robj + a, (size_t)(b - a) * 4);
+                foff[2 * v + 1] = at + (m - a);
+                at += b - a;
+                continue;
+            }
+            others.clear();
+            auto emit = [&](int32_t o) {
+                if (w->isplayer[o]) fobj[at++] = o;
+                else others.push_back(o);
+            };
+            const World::Seg* sg = p.seg >= 0 ? &w->segs[p.seg] : nullptr;
+            int32_t j = p.st0;
+            const int32_t je = p.st0 + p.st_n;
+            auto stints_to = [&](int32_t slot) {
+                for (; j < je && st[j].pos <= slot; j++)
+                    if (st[j].t_in < t && t < st[j].t_out) emit(st[j].obj);
+            };
+            for (int32_t k = 0; k < p.hi - p.lo; k++) {
+                stints_to(p.lo + k);
+                const int32_t o = sg->objs[k];
+                if (o == self) continue;
+                const auto it = left.find(o);
+                if (it == left.end() || it->second > t) emit(o);
+            }
+            stints_to(INT32_MAX);
+            foff[2 * v + 1] = at;
+            for (int32_t o : others) fobj[at++] = o;
+        }
+    }
+    foff[2 * n_v] = at;
+    out->visit_off = foff;
+    out->obj = fobj;
     return NFK_OK;
 }
 

@@ -2622,6 +2622,130 @@ __global__ __launch_bounds__(1024) void k_query_scan(const uint32_t* __restrict_
 }
 
 // ---------------------------------------------------------------------------------
+// View changes (nfk_view_changes): per visit (one group read by the AOI module at log instant t) the
+// group's players and its other objects as the group stood at that instant.  The frame-start
+// members are the group's slot range; tout[slot] is the log index at which the slot's object first
+// left (0xFFFFFFFF: it stays), and every later membership interval of the window is a stint of its
+// group, sorted by NFGUID, with pos = its lower-bound slot in the frame-start range.  A slot or
+// stint is live when t_in < t < t_out.  Shaped like k_query: k_view<false> counts each tile's two
+// lists (players at cnt[2 tile0 + x], others at cnt[2 tile0 + tiles + x]), k_query_scan scans the
+// counts, k_view<true> writes: a segment hit at slot s ranks behind the list's hits below it and its
+// live stints with pos <= s; a live stint ranks behind the hits below pos and the live stints before
+// it, and is written by the tile that holds pos (a visit with stints has the tile of `hi` as well).
+struct VDev {
+    int32_t lo, hi;     // the group's frame-start members' slots [lo, hi)
+    int32_t tile0;      // its first tile (the counts of its two lists sit at 2 * tile0)
+    int32_t tiles;
+    uint32_t t;         // the visit's instant (log index)
+    int32_t skip_slot;  // the entry's own object, -1: it has no frame-start slot
+    int32_t st0, st_n;  // the group's stints [st0, st0 + st_n), st_n <= kViewStints
+};
+struct VStint {
+    uint32_t obj;  // bit 31: a player
+    int32_t pos;
+    uint32_t t_in, t_out;
+};
+constexpr int kViewStints = 256;  // NFK_VC_STINT_CAP: one stint per lane of the workgroup
+static_assert(kViewStints == kTPB && kTile == kTPB, "k_view: a lane is a slot and a stint");
+
+__global__ __launch_bounds__(kTPB) void k_view_scatter(const int32_t* __restrict__ slot, const uint32_t* __restrict__ val,
+                                                       int n, uint32_t* __restrict__ tout, int cap) {
+    const int i = blockIdx.x * kTPB + threadIdx.x;
+    if (i >= n) return;
+    const int s = slot[i];
+    if (s >= 0 && s < cap) tout[s] = val ? val[i] : 0xFFFFFFFFu;
+}
+
+template <bool kWrite>
+__global__ __launch_bounds__(kTPB) void k_view(const VDev* __restrict__ vs, const VStint* __restrict__ st,
+                                               const uint64_t* __restrict__ fan_desc, const uint32_t* __restrict__ tout,
+                                               const int32_t* __restrict__ slot_obj, uint32_t* __restrict__ cnt,
+                                               const uint32_t* __restrict__ base, int32_t* __restrict__ out,
+                                               uint32_t out_cap) {
+    __shared__ uint32_t s_w[4][kTPB / 64];              // per wave: player hits, other hits, live player stints, others
+    __shared__ unsigned long long s_b[2][kTPB / 64];    // the hits' ballots
+    __shared__ int32_t s_pos[kViewStints];
+    __shared__ uint32_t s_pre[2][kViewStints + 1];      // live in-tile stints of a list before stint j
+    const VDev v = vs[blockIdx.y];
+    if ((int)blockIdx.x >= v.tiles) return;  // (uniform: the grid's x is the batch's longest range)
+    const int tid = threadIdx.x, w = tid >> 6;
+    const int s0 = v.lo + (int)blockIdx.x * kTile, slot = s0 + tid;
+    bool hit = false, player = false;
+    if (slot < v.hi && slot != v.skip_slot) {
+        const uint64_t desc = fan_desc[slot];
+        player = ((desc >> 46) & 0x3FFF) != 0;
+        hit = (uint32_t)(desc >> 60) != 0xF && tout[slot] > v.t;
+    }
+    const unsigned long long bp = __ballot(hit && player), bo = __ballot(hit && !player);
+    // this lane's stint: live at t, and its pos inside this tile
+    VStint x{0, 0, 0, 0};
+    bool sp = false, so = false;
+    if (tid < v.st_n) {
+        x = st[v.st0 + tid];
+        const bool in = x.pos >= s0 && x.pos < s0 + kTile && x.t_in < v.t && v.t < x.t_out;
+        sp = in && (x.obj >> 31);
+        so = in && !(x.obj >> 31);
+    }
+    const unsigned long long cp = __ballot(sp), co = __ballot(so);
+    if ((tid & 63) == 0) {
+        s_w[0][w] = (uint32_t)__builtin_popcountll(bp);
+        s_w[1][w] = (uint32_t)__builtin_popcountll(bo);
+        s_w[2][w] = (uint32_t)__builtin_popcountll(cp);
+        s_w[3][w] = (uint32_t)__builtin_popcountll(co);
+        s_b[0][w] = bp;
+        s_b[1][w] = bo;
+    }
+    if constexpr (kWrite) s_pos[tid] = tid < v.st_n ? x.pos : 0x7FFFFFFF;
+    __syncthreads();
+    if constexpr (!kWrite) {
+        if (tid < 2) {
+            uint32_t c = 0;
+            for (int i = 0; i < kTPB / 64; i++) c += s_w[tid][i] + s_w[2 + tid][i];
+            cnt[2 * v.tile0 + tid * v.tiles + (int)blockIdx.x] = c;
+        }
+    } else {
+        auto below = [&](unsigned long long b) {
+            return (uint32_t)__builtin_amdgcn_mbcnt_hi((uint32_t)(b >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)b, 0u));
+        };
+        // exclusive prefix of the live in-tile stints, per list (stints are in NFGUID order)
+        uint32_t ep = below(cp), eo = below(co);
+        for (int i = 0; i < w; i++) {
+            ep += s_w[2][i];
+            eo += s_w[3][i];
+        }
+        s_pre[0][tid + 1] = ep + (sp ? 1u : 0u);
+        s_pre[1][tid + 1] = eo + (so ? 1u : 0u);
+        if (tid == 0) s_pre[0][0] = s_pre[1][0] = 0;
+        __syncthreads();
+        const uint32_t b0 = base[2 * v.tile0 + (int)blockIdx.x], b1 = base[2 * v.tile0 + v.tiles + (int)blockIdx.x];
+        if (hit) {
+            const int l = player ? 0 : 1;
+            uint32_t r = (l ? b1 : b0) + below(l ? bo : bp);
+            for (int i = 0; i < w; i++) r += s_w[l][i];
+            if (v.st_n > 0) {
+                // the stints with pos <= slot: an upper bound in the sorted s_pos
+                int a = 0, b = v.st_n;
+                while (a < b) {
+                    const int m = (a + b) >> 1;
+                    if (s_pos[m] <= slot) a = m + 1;
+                    else b = m;
+                }
+                r += s_pre[l][a];
+            }
+            // (out_cap: the host's bound of the batch's entries; the host checks the total against it)
+            if (r < out_cap) out[r] = slot_obj[slot];
+        }
+        if (sp || so) {
+            const int l = sp ? 0 : 1, k = x.pos - s0;  // hits of the list at slots below pos
+            uint32_t r = (l ? b1 : b0) + (l ? eo : ep);
+            for (int i = 0; i < (k >> 6); i++) r += s_w[l][i];
+            if (k & 63) r += (uint32_t)__builtin_popcountll(s_b[l][k >> 6] & ((1ull << (k & 63)) - 1));
+            if (r < out_cap) out[r] = (int32_t)(x.obj & 0x7FFFFFFFu);
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------------
 // Record finds (nfk_find_rows): NFCRecord::FindInt / FindFloat (RC:830-899) of a batch of (object,
 // record, column, argument) queries.  A lane is a row: a query takes a group of G = 1 << lg lanes
 // (G: the power of two >= the batch's largest rows, so 64 / G queries per wave), every lane of the

@@ -60,8 +60,13 @@ bool linked_property(const void* self, size_t p) {
 }
 }  // namespace
 
+namespace {
+void drop_views(const void* self);  // (AddObjectEnterCallBack / AddObjectLeaveCallBack's table, below)
+}
+
 NFGPUKernelModule::~NFGPUKernelModule() {
     drop_links(this);
+    drop_views(this);
     WaitGather();
     pool_.reset();
     if (world_) nfk_destroy(world_);
@@ -680,6 +685,121 @@ static void* nfgpu_symbol(const char* name) {
     if (void* p = dlsym(RTLD_DEFAULT, name)) return p;
     if (void* h = dlopen("libnfgpu.so", RTLD_NOLOAD | RTLD_LAZY)) return dlsym(h, name);
     return nullptr;
+}
+
+// ---- view changes: AddObjectEnterCallBack / AddObjectLeaveCallBack (AOI:162-175, 292-529) ----
+// The callbacks are kept beside the modules, keyed by the module (the header's layout policy), as
+// LinkRecordColumns' state is; while no module of the process has one, Execute pays one atomic load.
+namespace {
+struct ViewCallbacks {
+    std::vector<NFGPUKernelModule::OBJECT_LIST_FUNCTOR> enter, leave;
+};
+std::mutex g_view_mu;
+std::unordered_map<const void*, ViewCallbacks> g_views;
+std::atomic<int> g_view_modules{0};
+
+void drop_views(const void* self) {
+    if (!g_view_modules.load(std::memory_order_acquire)) return;
+    std::lock_guard<std::mutex> lk(g_view_mu);
+    if (g_views.erase(self)) g_view_modules.fetch_sub(1, std::memory_order_release);
+}
+bool add_view_callback(const void* self, const NFGPUKernelModule::OBJECT_LIST_FUNCTOR& cb, bool enter) {
+    if (!cb) return false;
+    std::lock_guard<std::mutex> lk(g_view_mu);
+    auto ins = g_views.emplace(self, ViewCallbacks{});
+    if (ins.second) g_view_modules.fetch_add(1, std::memory_order_release);
+    (enter ? ins.first->second.enter : ins.first->second.leave).push_back(cb);
+    return true;
+}
+}  // namespace
+
+bool NFGPUKernelModule::AddObjectEnterCallBack(const OBJECT_LIST_FUNCTOR& cb) { return add_view_callback(this, cb, true); }
+bool NFGPUKernelModule::AddObjectLeaveCallBack(const OBJECT_LIST_FUNCTOR& cb) { return add_view_callback(this, cb, false); }
+
+void NFGPUKernelModule::DeliverViewChanges() {
+    if (!g_view_modules.load(std::memory_order_acquire) || !committed_) return;
+    ViewCallbacks cbs;
+    {
+        std::lock_guard<std::mutex> lk(g_view_mu);
+        auto it = g_views.find(this);
+        if (it == g_views.end()) return;
+        cbs = it->second;  // (a callback may register another: this delivery keeps its own list)
+    }
+    using Fn = int (*)(void*, nfk_view_changes_result*);
+    static const Fn fn = (Fn)nfgpu_symbol("nfk_view_changes");
+    if (!fn) throw std::runtime_error("nfk_view_changes: the nfgpu library has no such entry point");
+    Flush();
+    nfk_view_changes_result r{};
+    check(fn(world_, &r), "nfk_view_changes");
+    if (r.n_calls == 0) return;
+    WaitGather();  // (the gather's workers read guids_)
+    // the result is the world's until the next call: a callback may make one, so the lists are copied
+    struct Lists { std::vector<NFGUID> players, all; };
+    std::vector<nfk_vc_entry> log(r.log, r.log + r.n_calls);
+    std::vector<uint32_t> cv(r.call_visit, r.call_visit + r.n_calls + 1);
+    std::vector<Lists> vl((size_t)r.n_visits);
+    for (int32_t v = 0; v < r.n_visits; v++) {
+        const uint32_t a = r.visit_off[2 * v], m = r.visit_off[2 * v + 1], b = r.visit_off[2 * v + 2];
+        for (uint32_t i = a; i < b; i++) {
+            const NFGUID& g = guids_[(size_t)r.obj[i]];
+            if (i < m) vl[(size_t)v].players.push_back(g);
+            vl[(size_t)v].all.push_back(g);  // players then others (KM:1169-1199)
+        }
+    }
+    auto Enter = [&](const std::vector<NFGUID>& to, const std::vector<NFGUID>& about) {
+        for (auto& cb : cbs.enter) cb(to, about);
+    };
+    auto Leave = [&](const std::vector<NFGUID>& to, const std::vector<NFGUID>& about) {
+        for (auto& cb : cbs.leave) cb(to, about);
+    };
+    static const Lists kNone;
+    for (int32_t i = 0; i < r.n_calls; i++) {
+        const nfk_vc_entry& e = log[(size_t)i];
+        const std::vector<NFGUID> self{guids_[(size_t)e.obj]};
+        const bool player = isplayer_[(size_t)e.obj] != 0;
+        uint32_t v = cv[(size_t)i];
+        auto next = [&]() -> const Lists& { return vl[(size_t)v++]; };
+        // OnGroupEvent's leaving half (AOI:361-387): both calls only when the old group is not empty
+        auto group_leave = [&](const Lists& l) {
+            if (l.all.empty()) return;
+            Leave(l.players, self);
+            Leave(self, l.all);
+        };
+        // ... its entering half (AOI:396-437)
+        auto group_enter = [&](const Lists& l) {
+            if (!l.players.empty()) Enter(l.players, self);
+            if (!l.all.empty() && player) Enter(self, l.all);
+        };
+        // OnSceneEvent (AOI:506-513): the Leave even when the old list is empty; AOI:508 tests the
+        // players WITH self, who is in the new scene's group 0 only when it was created there
+        auto scene_event = [&](const Lists& old, const Lists& now, bool self_in_new) {
+            Leave(self, old.all);
+            if (!now.players.empty() || (self_in_new && player)) Enter(now.players, self);
+            Enter(self, now.all);
+        };
+        switch (e.kind) {
+        case NFK_VC_SWITCH:
+            if (e.from_group > 0) group_leave(next());
+            if (e.from_scene != e.to_scene) {
+                const Lists& old = next();
+                scene_event(old, next(), false);
+            }
+            if (e.to_group > 0) group_enter(next());
+            break;
+        case NFK_VC_DESTROY:  // COE_DESTROY (AOI:294-327): the Leave even when nobody is told
+            if (e.from_scene > 0) Leave(next().players, self);
+            break;
+        case NFK_VC_CREATE:   // the SceneID, then GroupID writes of KM:248-249, then COE_CREATE_HASDATA (AOI:341)
+            if (e.to_scene != 0) scene_event(kNone, next(), e.to_group == 0);
+            if (e.to_group > 0) group_enter(next());
+            if (player) Enter(self, self);
+            break;
+        default:              // NFK_VC_EXPORT: the leaving half of a cross-scene switch
+            if (e.from_group > 0) group_leave(next());
+            Leave(self, next().all);
+            break;
+        }
+    }
 }
 
 bool NFGPUKernelModule::RunQueries(const nfk_query* q, int n, std::vector<NFGUID>& list) {
@@ -1542,6 +1662,7 @@ bool NFGPUKernelModule::Execute() {
     stats_ = FrameStats{};
     if (shard_) MigrateShard(false);
     Flush();
+    DeliverViewChanges();  // (the window's enter / leave lists, while its membership log is still there)
     check(nfk_execute(world_, clock_()), "nfk_execute");
     pending_calls_ = 0;
     touched_.clear();
@@ -1663,6 +1784,7 @@ bool NFGPUKernelModule::Execute() {
 // events delivered
 void NFGPUKernelModule::CallsPass() {
     Flush();
+    DeliverViewChanges();
     check(nfk_execute_calls(world_), "nfk_execute_calls");
     pending_calls_ = 0;
     touched_.clear();

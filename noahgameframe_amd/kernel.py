@@ -70,6 +70,21 @@ class QueryResult(ctypes.Structure):
                 ("bytes", ctypes.c_int64)]
 
 
+class ViewChanges(ctypes.Structure):
+    """nfk_view_changes_result (include/nfgpu.h)"""
+    _fields_ = [("n_calls", ctypes.c_int32), ("n_visits", ctypes.c_int32), ("log", ctypes.POINTER(ctypes.c_int32)),
+                ("call_visit", ctypes.POINTER(ctypes.c_uint32)), ("visit", ctypes.POINTER(ctypes.c_int32)),
+                ("visit_off", ctypes.POINTER(ctypes.c_uint32)), ("obj", ctypes.POINTER(ctypes.c_int32)),
+                ("kernel_ms", ctypes.c_double), ("bytes", ctypes.c_int64), ("n_host", ctypes.c_int32),
+                ("n_tiles", ctypes.c_int32)]
+
+
+# nfk_vc_entry::kind, nfk_vc_visit::why
+VC_SWITCH, VC_DESTROY, VC_CREATE, VC_EXPORT = 0, 1, 2, 3
+VC_GROUP_LEAVE, VC_GROUP_ENTER, VC_SCENE_LEAVE, VC_SCENE_ENTER, VC_WHY_DESTROY = 0, 1, 2, 3, 4
+VC_STINT_CAP = 256   # NFK_VC_STINT_CAP
+
+
 class Snapshot(ctypes.Structure):
     _U32, _I32, _U64 = ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_uint64)
     _fields_ = [("p_first", _U32), ("p_count", _U32), ("p_pid", _I32), ("p_bits", _U64), ("p_head", _U64),
@@ -155,6 +170,7 @@ def load_library(path=LIB_PATH):
         "nfk_find_objects_obj": [VP, I32, VP, VP, VP, VP, VP, VP], "nfk_read_rec_events_obj": [VP, VP, VP],
         "nfk_swap_rows": [VP, I32, VP, VP, VP, VP, VP],
         "nfk_link_record": [VP, I32, I32, VP, I32],
+        "nfk_view_changes": [VP, P(ViewChanges)],
     }
     for name, args in sig.items():
         if not hasattr(lib, name) and os.environ.get("NFGPU_LIB"):
@@ -786,6 +802,27 @@ class NFKernelModule:
     def GetSceneOnLineList(self, scene, guid_head, guid_data):
         """NFCKernelModule::GetSceneOnLineList (KM:1042): the players of every group of the scene"""
         return self._guids(self.query_objects([query(scene)])[0], guid_head, guid_data)
+
+    # ---- view changes (NFCSceneAOIModule::OnGroupEvent / OnSceneEvent / OnClassCommonEvent, AOI:292-529) ----
+    def view_changes(self):
+        """nfk_view_changes: the window's membership log and, per visit, the group's players and its
+        other objects as of the visit's call.  A dict of numpy arrays: log [n_calls, 6] (object, kind,
+        from scene, from group, to scene, to group), call_visit [n_calls + 1], visit [n_visits, 3]
+        (why, scene, group), visit_off [2 n_visits + 1] into obj (players of visit v at
+        obj[off[2v]:off[2v + 1]], others at obj[off[2v + 1]:off[2v + 2]]); and kernel_ms, bytes,
+        n_host, n_tiles."""
+        res = ViewChanges()
+        self._chk(self.lib.nfk_view_changes(self.h, ctypes.byref(res)))
+        n, nv = res.n_calls, res.n_visits
+        arr = np.ctypeslib.as_array
+        log = arr(res.log, (n, 6)).copy() if n else np.zeros((0, 6), np.int32)
+        cv = arr(res.call_visit, (n + 1,)).copy() if n else np.zeros(1, np.uint32)
+        vis = arr(res.visit, (nv, 3)).copy() if nv else np.zeros((0, 3), np.int32)
+        off = arr(res.visit_off, (2 * nv + 1,)).copy() if nv else np.zeros(1, np.uint32)
+        tot = int(off[-1])
+        obj = arr(res.obj, (tot,)).copy() if tot else np.zeros(0, np.int32)
+        return {"log": log, "call_visit": cv, "visit": vis, "visit_off": off, "obj": obj,
+                "kernel_ms": res.kernel_ms, "bytes": res.bytes, "n_host": res.n_host, "n_tiles": res.n_tiles}
 
     def online_count(self, scene=-1, group=-1):
         n = ctypes.c_int32()
