@@ -468,6 +468,46 @@ public:
     // object column cannot be linked (std::invalid_argument): a Swap event names the column whose index is
     // its target row, which is the reference's logical column and the device's physical one.
     void LinkRecordColumns(const std::string& strRecordName, int rows, const std::vector<std::string>& propertyNames);
+    // NFCPropertyModule's resource calls (NFCPropertyModule.cpp:215-472) on the device (nfk_adjust_props):
+    // a batch of n calls, op[i] one of NFK_ADJ_*, dst[i] / bound[i] int property NAMES resolved once per
+    // distinct name (bound "" where the op reads no maximum), applied in array order; ret[i] is
+    // nfk_adjust_props' result byte (bit 0 the reference's return value, bit 1 a Set was queued).  The
+    // buffered SetProperty* calls are handed over first, as before a Get*, so every call sees them.  A
+    // call on an object this module does not have answers as the reference does — GetPropertyInt gives 0
+    // there and the Set is dropped — and queues nothing.  False, with nothing queued, before AfterInit,
+    // for a name that is no int property, a linked dst, or a bound that does not fit the op.  The entry
+    // point is looked up at first use; a library without it: std::runtime_error.
+    // LIMITATION: inside a heartbeat functor with walk-order reads on, GetPropertyInt of a
+    // program-written property answers from the frame's per-Set log (WalkRead); a resource call made there
+    // does not: it reads the world as nfk_get_props does (the frame's final values and the queued Sets)
+    // and only marks its dst as written by the walk.  A functor that needs the walk-order value spells
+    // the call out with GetPropertyInt / SetPropertyInt.
+    bool AdjustProperties(int n, const NFGUID* guids, const uint8_t* op, const std::string* dst, const std::string* bound,
+                          const int64_t* value, uint8_t* ret);
+    // NFIPropertyModule's names, one call (FullHPMP two) each, on the properties HP / MAXHP, MP / MAXMP,
+    // SP / MAXSP, Gold (Money calls) and Money (Diamond calls): NFrame::Player's naming.
+    // SetResourcePropertyNames replaces them, once, before AfterInit (kept beside the module).  FullHPMP
+    // returns true whatever its two fills answer; AddMoney / AddDiamond return false on both branches.
+    void SetResourcePropertyNames(const std::string& hp, const std::string& maxhp, const std::string& mp,
+                                  const std::string& maxmp, const std::string& sp, const std::string& maxsp,
+                                  const std::string& gold, const std::string& money);
+    bool FullHPMP(const NFGUID& self);
+    bool FullSP(const NFGUID& self);
+    bool AddHP(const NFGUID& self, int64_t nValue);
+    bool ConsumeHP(const NFGUID& self, int64_t nValue);
+    bool EnoughHP(const NFGUID& self, int64_t nValue);
+    bool AddMP(const NFGUID& self, int64_t nValue);
+    bool ConsumeMP(const NFGUID& self, int64_t nValue);
+    bool EnoughMP(const NFGUID& self, int64_t nValue);
+    bool AddSP(const NFGUID& self, int64_t nValue);
+    bool ConsumeSP(const NFGUID& self, int64_t nValue);
+    bool EnoughSP(const NFGUID& self, int64_t nValue);
+    bool AddMoney(const NFGUID& self, int64_t nValue);
+    bool ConsumeMoney(const NFGUID& self, int64_t nValue);
+    bool EnoughMoney(const NFGUID& self, int64_t nValue);
+    bool AddDiamond(const NFGUID& self, int64_t nValue);
+    bool ConsumeDiamond(const NFGUID& self, int64_t nValue);
+    bool EnoughDiamond(const NFGUID& self, int64_t nValue);
     bool IsUsed(const NFGUID& self, const std::string& strRecordName, int nRow);
     // NFIKernelModule::GetRecordInt / GetRecordFloat (NFIKernelModule.h:134-135): read-your-writes
     // like GetProperty*; 0 for an unused row (NFCRecord::GetInt, RC:623)

@@ -733,6 +733,69 @@ int nfk_find_objects_obj(void* world, int32_t n, const int32_t* obj, const int32
  * host (each pointer may be null) */
 int nfk_find_stats(void* world, double* kernel_ms, int64_t* bytes, int32_t* n_host);
 
+/* ---- resource calls: NFCPropertyModule's FullHPMP / AddHP / ConsumeHP / EnoughHP / AddMoney ...
+ * (PM:215-472), each a read-modify-write of one int property dst, some against a second one, bound.
+ * A batch of n calls applies in array order and returns, and leaves the world, exactly as this loop
+ * over the entry points above would: cur = nfk_get_props(o, dst), max = nfk_get_props(o, bound),
+ * the op's rule, nfk_set_props(o, dst, new) where the reference calls SetPropertyInt.  So a call
+ * sees the device's values, the window's queued Sets and linked-record calls, the objects spawned
+ * or imported in this window and every earlier call of its batch.  value is signed 64-bit; add and
+ * subtract wrap (signed overflow is undefined in the reference).
+ *   op                   reference                   rule (v = value[i])
+ *   NFK_ADJ_GAIN_ALIVE   AddHP PM:232                v <= 0: ret 0, nothing.  Else ret 1, and if
+ *                                                    cur > 0: n = cur + v, n = max if n > max, Set(n)
+ *   NFK_ADJ_GAIN_CAP     AddMP / AddSP PM:281, 340   v <= 0: ret 0.  Else n = cur + v capped at max,
+ *                                                    Set(n), ret 1 (no cur > 0 test)
+ *   NFK_ADJ_GAIN         AddMoney / AddDiamond       v <= 0: ret 0.  Else Set(cur + v), ret 0 (the
+ *                        PM:386, 430                 reference returns false on both branches)
+ *   NFK_ADJ_SPEND_ALIVE  ConsumeHP/MP/SP             cur > 0 && cur - v >= 0: Set(cur - v), ret 1.
+ *                        PM:267, 302, 361            Else ret 0.  v is not tested (v < 0 raises dst)
+ *   NFK_ADJ_SPEND        ConsumeMoney / Diamond      v <= 0: ret 0.  Else n = cur - v; n >= 0:
+ *                        PM:400, 444                 Set(n), ret 1; else ret 0
+ *   NFK_ADJ_ENOUGH       every Enough* PM:256...     ret = cur > 0 && cur - v >= 0.  Never Sets
+ *   NFK_ADJ_FILL         FullSP, each half of        max > 0: Set(max), ret 1.  Else ret 0.  v ignored
+ *                        FullHPMP PM:215, 327
+ * ret[i]: bit 0 the reference's return value, bit 1 a Set was queued (a Set of the value the
+ * property already holds is queued too, as the reference still calls SetPropertyInt; the frame's
+ * change predicate drops it).  The accepted Sets join the window's SetProperty stream in batch
+ * order, exactly as nfk_set_props' would.
+ * dst is an int property nfk_set_props accepts (a linked property or an object property is refused
+ * with that call's NFK_ERR_ARG); bound is an int property (a linked one too) for GAIN_ALIVE,
+ * GAIN_CAP and FILL and -1 for the four ops that read no maximum, else NFK_ERR_ARG.  An unknown or
+ * destroyed object is NFK_ERR_NOTFOUND; before nfk_commit NFK_ERR_STATE.  The whole batch is
+ * checked before anything is queued.
+ * One launch for the batch (k_adjust, the world's stream) and one pinned copy back: the host groups
+ * the calls stably by (object, dst), a group's first lane walks it with cur in a register.  A call
+ * whose (object, dst), (object, bound) or object has pending state in this window — a queued Set,
+ * a linked bound whose record has queued calls, an object spawned or imported in the window — or
+ * whose bound is another call's dst in the batch, is answered on the host through nfk_get_props'
+ * code, with the other calls on its dst (and on its bound).  After an adjust batch its (object, dst)
+ * pairs have queued Sets, so later batches of the window on them run on the host.
+ * nfk_adjust_props_obj takes object indices (nfk_query_objects' hits, ev_obj) instead of NFGUIDs. */
+#define NFK_ADJ_GAIN_ALIVE 0
+#define NFK_ADJ_GAIN_CAP 1
+#define NFK_ADJ_GAIN 2
+#define NFK_ADJ_SPEND_ALIVE 3
+#define NFK_ADJ_SPEND 4
+#define NFK_ADJ_ENOUGH 5
+#define NFK_ADJ_FILL 6
+#define NFK_ADJ_RET 1    /* ret bit 0: the reference's return value */
+#define NFK_ADJ_SET 2    /* ret bit 1: a Set was queued */
+int nfk_adjust_props(void* world, int32_t n, const int64_t* guid_head, const int64_t* guid_data, const uint8_t* op,
+                     const int32_t* dst, const int32_t* bound, const int64_t* value, uint8_t* ret);
+int nfk_adjust_props_obj(void* world, int32_t n, const int32_t* obj, const uint8_t* op, const int32_t* dst,
+                         const int32_t* bound, const int64_t* value, uint8_t* ret);
+/* the last nfk_adjust_props / nfk_adjust_props_obj of the world */
+typedef struct nfk_adjust_stats_t {
+    double kernel_ms;   /* the launch's device time (0 unless nfk_set_profiling is on) */
+    int64_t bytes;      /* read back from the device */
+    int32_t n_dev;      /* calls answered by k_adjust */
+    int32_t n_host;     /* calls answered on the host */
+    int32_t n_set;      /* Sets queued */
+    int32_t pad;
+} nfk_adjust_stats_t;
+int nfk_adjust_stats(void* world, nfk_adjust_stats_t* out);
+
 /* ---- enter snapshots: the payloads of NFCGameServerNet_ServerModule::OnPropertyEnter (:271-393) and
  * OnRecordEnter (:395-554), which NFCSceneAOIModule::OnGroupEvent / OnSceneEvent / OnClassCommonEvent
  * hand to the recipients of an object that comes into view ----

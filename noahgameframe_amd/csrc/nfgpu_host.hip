@@ -369,6 +369,15 @@ struct World {
     double f_kernel_ms = 0;
     int64_t f_bytes = 0;
     int32_t f_host = 0;
+    // resource calls (nfk_adjust_props): the batch's descriptors and results on the device and in
+    // pinned host memory (descriptors, new values, result bytes), both grown on demand; the last
+    // call's figures for nfk_adjust_stats
+    void* a_dev = nullptr;
+    size_t a_dcap = 0;
+    char* a_pin = nullptr;
+    size_t a_pcap = 0;
+    hipEvent_t a_ev[2] = {nullptr, nullptr};
+    nfk_adjust_stats_t a_stats{};
     // enter snapshots (nfk_snapshot_objects): the walk's order (empty: id order), its table on the
     // device (rebuilt when flags or order change), the batch's scratch (requests, counts, bases) and
     // result region on the device, and the pinned buffer the nfk_snapshot pointers index
@@ -1941,6 +1950,10 @@ int nfk_destroy(void* world) {
     if (w->f_dev) (void)hipFree(w->f_dev);
     if (w->f_pin) (void)hipHostFree(w->f_pin);
     for (auto e : w->f_ev)
+        if (e) (void)hipEventDestroy(e);
+    if (w->a_dev) (void)hipFree(w->a_dev);
+    if (w->a_pin) (void)hipHostFree(w->a_pin);
+    for (auto e : w->a_ev)
         if (e) (void)hipEventDestroy(e);
     if (w->s_tab_d) (void)hipFree(w->s_tab_d);
     if (w->s_dev) (void)hipFree(w->s_dev);
@@ -3656,6 +3669,244 @@ int nfk_get_props(void* world, int32_t n, const int64_t* gh, const int64_t* gd, 
         if (pid[i] < 0 || pid[i] >= w->n_if) return fail(NFK_ERR_ARG, "bad property id (object properties: nfk_get_objects)");
     }
     return current_props(w, n, obj.data(), pid, bits);
+}
+
+// ---- resource calls (nfk_adjust_props): NFCPropertyModule's Add* / Consume* / Enough* / Full* (PM:215-472) ----
+// the calls of resolved objects (obj[i] < 0: unknown; gh / gd for the message, or null)
+static int adjust_props(World* w, int32_t n, const int32_t* obj, const int64_t* gh, const int64_t* gd, const uint8_t* op,
+                        const int32_t* dst, const int32_t* bound, const int64_t* value, uint8_t* ret) {
+    w->a_stats = nfk_adjust_stats_t{};
+    // the whole batch is checked before anything is read or queued
+    for (int32_t i = 0; i < n; i++) {
+        if (obj[i] < 0)
+            return fail(NFK_ERR_NOTFOUND, gh ? "There is no object " + std::to_string(gh[i]) + "-" + std::to_string(gd[i])
+                                             : "no object index");
+        if (op[i] > NFK_ADJ_FILL) return fail(NFK_ERR_ARG, "unknown resource call op " + std::to_string(op[i]));
+        if (dst[i] < 0 || dst[i] >= w->n_if)
+            return fail(NFK_ERR_ARG, dst[i] >= w->n_if && dst[i] < w->n_prop ? "object property: use nfk_set_objects"
+                                                                              : "bad property id");
+        if (dst[i] >= w->cfg.n_int) return fail(NFK_ERR_ARG, "a resource call's dst is an int property");
+        if (w->linked_pid(dst[i]))
+            return fail(NFK_ERR_ARG, "property " + std::to_string(dst[i]) + " is linked to a record column (nfk_link_record): "
+                                     "its value is its link's");
+        const bool takes = op[i] == NFK_ADJ_GAIN_ALIVE || op[i] == NFK_ADJ_GAIN_CAP || op[i] == NFK_ADJ_FILL;
+        if (takes ? (bound[i] < 0 || bound[i] >= w->cfg.n_int) : bound[i] != -1)
+            return fail(NFK_ERR_ARG, takes ? "this resource call's bound is an int property" : "this resource call takes no bound (-1)");
+        if (w->src_row[obj[i]] < 0 && w->slot_of_obj[obj[i]] < 0) return fail(NFK_ERR_STATE, "object without a slot");
+    }
+    if (n == 0) return NFK_OK;
+
+    // the calls grouped stably by (object, dst): ord[] lists them group by group in call order,
+    // gkey[] the groups' keys ascending, gat[] where each group starts in ord[].  (A batch whose
+    // keys ascend strictly, distinct objects in index order, is its own grouping.)
+    // (keys as ov_last's / dcache's: object << 7 | pid; the int and f64 properties are at most 128)
+    static_assert(NFK_MAX_PROPS <= 128, "(object << 7 | pid) keys and the two-word dst_pids hold 128 property ids");
+    auto key_of = [&](int32_t i, int32_t pid) { return ((uint64_t)(uint32_t)obj[i] << 7) | (uint32_t)pid; };
+    bool ascending = true;
+    uint64_t dst_pids[2] = {0, 0};
+    for (int32_t i = 0; i < n; i++) {
+        dst_pids[dst[i] >> 6] |= 1ull << (dst[i] & 63);
+        if (i && key_of(i, dst[i]) <= key_of(i - 1, dst[i - 1])) ascending = false;
+    }
+    std::vector<uint32_t> ord(n);
+    if (ascending) {
+        for (int32_t i = 0; i < n; i++) ord[i] = (uint32_t)i;
+    } else {
+        const int ib = bits_for((uint64_t)n - 1), kb = bits_for((uint64_t)w->n_obj) + 7;
+        if (ib + kb <= 64) {
+            std::vector<uint64_t> a(n), t;
+            for (int32_t i = 0; i < n; i++) a[i] = (key_of(i, dst[i]) << ib) | (uint32_t)i;
+            radix_sort_packed(a, t, ib, kb);
+            for (int32_t i = 0; i < n; i++) ord[i] = (uint32_t)(a[i] & ((1ull << ib) - 1));
+        } else {
+            for (int32_t i = 0; i < n; i++) ord[i] = (uint32_t)i;
+            std::stable_sort(ord.begin(), ord.end(),
+                             [&](uint32_t x, uint32_t y) { return key_of((int32_t)x, dst[x]) < key_of((int32_t)y, dst[y]); });
+        }
+    }
+    std::vector<uint64_t> gkey;
+    std::vector<uint32_t> gat;
+    for (int32_t k = 0; k < n; k++) {
+        const uint64_t key = key_of((int32_t)ord[k], dst[ord[k]]);
+        if (gkey.empty() || gkey.back() != key) {
+            gkey.push_back(key);
+            gat.push_back((uint32_t)k);
+        }
+    }
+    gat.push_back((uint32_t)n);
+    const size_t ng = gkey.size();
+
+    // the groups answered on the host: a call with pending state in this window on its (object,
+    // dst), its (object, bound) or its object, and a call whose bound is a dst of this batch — with
+    // that dst's group, so that the device's groups depend on no host call and the reverse
+    if (int r = index_queued_sets(w)) return r;
+    const bool queued = !w->ov_last.empty(), recq = !w->rq_index.empty() && (w->lk_pids[0] | w->lk_pids[1]);
+    std::vector<uint8_t> ghost(ng, 0);
+    auto group_of = [&](uint64_t key) -> int64_t {
+        auto it = std::lower_bound(gkey.begin(), gkey.end(), key);
+        return it != gkey.end() && *it == key ? (int64_t)(it - gkey.begin()) : -1;
+    };
+    int32_t n_host = 0;
+    for (size_t g = 0; g < ng; g++)
+        for (uint32_t k = gat[g]; k < gat[g + 1]; k++) {
+            const int32_t i = (int32_t)ord[k], o = obj[i], b = bound[i];
+            bool pend = w->src_row[o] >= 0 || (queued && w->ov_last.count(gkey[g]));
+            if (b >= 0) {
+                const uint64_t bk = key_of(i, b);
+                pend = pend || (queued && w->ov_last.count(bk));
+                if (recq && w->linked_pid(b))
+                    pend = pend || w->rq_index.count(((uint64_t)o << 3) | (uint32_t)(w->lk_of_pid[b] >> 4));
+                if ((dst_pids[b >> 6] >> (b & 63)) & 1) {
+                    const int64_t bg = group_of(bk);
+                    if (bg >= 0) {
+                        ghost[bg] = 1;
+                        pend = true;
+                    }
+                }
+            }
+            if (pend) ghost[g] = 1;
+        }
+    for (size_t g = 0; g < ng; g++)
+        if (ghost[g]) n_host += (int32_t)(gat[g + 1] - gat[g]);
+    const int32_t nd = n - n_host;
+
+    // the device's calls: descriptors in pinned memory, the new values and result bytes behind them
+    const size_t o_v = align16((size_t)nd * sizeof(AdjDev)), o_r = o_v + (size_t)n * 8, tot = align16(o_r + (size_t)n);
+    std::vector<int64_t> newv_h;  // (the host's calls' new values, by place)
+    const int64_t* newv = nullptr;
+    if (nd) {
+        if (int r = dev_reserve(w, &w->a_dev, &w->a_dcap, tot)) return r;
+        if (tot > w->a_pcap) {
+            if (w->a_pin) HIPCHK(hipHostFree(w->a_pin));
+            w->a_pin = nullptr;
+            const size_t c = std::max(tot, w->a_pcap + w->a_pcap / 2);
+            w->a_pcap = 0;  // (until the new buffer exists)
+            HIPCHK(hipHostMalloc((void**)&w->a_pin, c, hipHostMallocDefault));
+            w->a_pcap = c;
+        }
+        AdjDev* hq = (AdjDev*)w->a_pin;
+        int32_t q = 0;
+        for (size_t g = 0; g < ng; g++) {
+            if (ghost[g]) continue;
+            for (uint32_t k = gat[g]; k < gat[g + 1]; k++) {
+                const int32_t i = (int32_t)ord[k], o = obj[i];
+                const int64_t sl = w->slot_of_obj[o];  // (not entered in this window: it has a slot)
+                AdjDev f;
+                f.dst = (uint64_t)(uintptr_t)(w->d.pmem + w->tab.p_off[dst[i]] + sl * w->tab.p_str[dst[i]]);
+                f.bound = bound[i] < 0 ? 0 : (uint64_t)(uintptr_t)(w->d.pmem + w->tab.p_off[bound[i]] + sl * w->tab.p_str[bound[i]]);
+                f.v = value[i];
+                f.place = (uint32_t)i;
+                f.len = k == gat[g] ? gat[g + 1] - gat[g] : 0;
+                f.op = op[i];
+                f.pad = 0;
+                hq[q++] = f;
+            }
+        }
+        char* D = (char*)w->a_dev;
+        const bool timed = w->profiling;
+        if (timed)
+            for (auto& e : w->a_ev)
+                if (!e) HIPCHK(hipEventCreate(&e));
+        HIPCHK(hipMemcpyAsync(D, w->a_pin, (size_t)nd * sizeof(AdjDev), hipMemcpyHostToDevice, w->stream));
+        // (a place no lane stores to keeps 0xFF: a descriptor k_adjust refused is an error, not a stale result)
+        HIPCHK(hipMemsetAsync(D + o_r, 0xFF, (size_t)n, w->stream));
+        if (timed) HIPCHK(hipEventRecord(w->a_ev[0], w->stream));
+        hipLaunchKernelGGL(k_adjust, dim3((unsigned)((nd + kTPB - 1) / kTPB)), dim3(kTPB), 0, w->stream, (const AdjDev*)D, nd,
+                           n, (int64_t*)(D + o_v), (uint8_t*)(D + o_r));
+        HIPCHK(hipGetLastError());
+        if (timed) HIPCHK(hipEventRecord(w->a_ev[1], w->stream));
+        HIPCHK(hipMemcpyAsync(w->a_pin + o_v, D + o_v, tot - o_v, hipMemcpyDeviceToHost, w->stream));
+        HIPCHK(hipStreamSynchronize(w->stream));
+        w->a_stats.bytes = (int64_t)(tot - o_v);
+        if (timed) {
+            float ms = 0;
+            HIPCHK(hipEventElapsedTime(&ms, w->a_ev[0], w->a_ev[1]));
+            w->a_stats.kernel_ms = ms;
+        }
+        newv = (const int64_t*)(w->a_pin + o_v);
+        const uint8_t* hr = (const uint8_t*)(w->a_pin + o_r);
+        uint8_t unset = 0;
+        for (size_t g = 0; g < ng; g++)
+            if (!ghost[g])
+                for (uint32_t k = gat[g]; k < gat[g + 1]; k++) {
+                    ret[ord[k]] = hr[ord[k]];
+                    unset |= hr[ord[k]] & 0xFC;
+                }
+        if (unset) return fail(NFK_ERR_DEVICE, "k_adjust left a call unanswered (nothing of the batch queued)");
+    }
+
+    // the host's calls, in batch order over the values nfk_get_props answers (read once per cell)
+    if (n_host) {
+        std::vector<uint8_t> chost(n, 0);
+        for (size_t g = 0; g < ng; g++)
+            if (ghost[g])
+                for (uint32_t k = gat[g]; k < gat[g + 1]; k++) chost[ord[k]] = 1;
+        std::unordered_map<uint64_t, int64_t> cell;
+        std::vector<int32_t> ro, rp;
+        for (int32_t i = 0; i < n; i++) {
+            if (!chost[i]) continue;
+            for (int32_t p : {dst[i], bound[i]})
+                if (p >= 0 && cell.emplace(key_of(i, p), 0).second) {
+                    ro.push_back(obj[i]);
+                    rp.push_back(p);
+                }
+        }
+        std::vector<uint64_t> got(ro.size());
+        if (int r = current_props(w, (int32_t)ro.size(), ro.data(), rp.data(), got.data())) return r;
+        for (size_t q = 0; q < ro.size(); q++) cell[((uint64_t)(uint32_t)ro[q] << 7) | (uint32_t)rp[q]] = (int64_t)got[q];
+        newv_h.assign(n, 0);
+        if (newv) memcpy(newv_h.data(), newv, (size_t)n * 8);
+        for (int32_t i = 0; i < n; i++) {
+            if (!chost[i]) continue;
+            int64_t& cur = cell[key_of(i, dst[i])];
+            const int64_t mx = bound[i] < 0 ? 0 : cell[key_of(i, bound[i])];
+            int64_t nv = cur;
+            const uint32_t r = adj_rule(op[i], cur, mx, value[i], &nv);
+            if (r & NFK_ADJ_SET) cur = nv;
+            newv_h[i] = nv;
+            ret[i] = (uint8_t)r;
+        }
+        newv = newv_h.data();
+    }
+
+    // the accepted Sets join the window's SetProperty stream in batch order
+    std::vector<int32_t> so, sp;
+    std::vector<uint64_t> sb;
+    for (int32_t i = 0; i < n; i++)
+        if (ret[i] & NFK_ADJ_SET) {
+            so.push_back(obj[i]);
+            sp.push_back(dst[i]);
+            sb.push_back((uint64_t)newv[i]);
+        }
+    w->a_stats.n_dev = nd;
+    w->a_stats.n_host = n_host;
+    w->a_stats.n_set = (int32_t)so.size();
+    return queue_sets(w, (int32_t)so.size(), so.data(), sp.data(), sb.data(), nullptr, nullptr);
+}
+
+int nfk_adjust_props(void* world, int32_t n, const int64_t* gh, const int64_t* gd, const uint8_t* op, const int32_t* dst,
+                     const int32_t* bound, const int64_t* value, uint8_t* ret) {
+    World* w = (World*)world;
+    if (!w || n < 0 || (n && (!gh || !gd || !op || !dst || !bound || !value || !ret))) return fail(NFK_ERR_ARG, "null argument");
+    if (!w->committed) return fail(NFK_ERR_STATE, "commit first");
+    w->look.resize(n);  // one GUID lookup per call
+    if (int rl = find_many_par(w, n, gh, gd, w->look.data())) return rl;
+    return adjust_props(w, n, w->look.data(), gh, gd, op, dst, bound, value, ret);
+}
+
+int nfk_adjust_props_obj(void* world, int32_t n, const int32_t* obj, const uint8_t* op, const int32_t* dst,
+                         const int32_t* bound, const int64_t* value, uint8_t* ret) {
+    World* w = (World*)world;
+    if (!w || n < 0 || (n && (!obj || !op || !dst || !bound || !value || !ret))) return fail(NFK_ERR_ARG, "null argument");
+    if (!w->committed) return fail(NFK_ERR_STATE, "commit first");
+    return adjust_props(w, n, live_objects(w, n, obj), nullptr, nullptr, op, dst, bound, value, ret);
+}
+
+int nfk_adjust_stats(void* world, nfk_adjust_stats_t* out) {
+    World* w = (World*)world;
+    if (!w || !out) return fail(NFK_ERR_ARG, "null argument");
+    *out = w->a_stats;
+    return NFK_OK;
 }
 
 // ---- enter snapshots (nfk_snapshot_objects): OnPropertyEnter / OnRecordEnter payloads ----

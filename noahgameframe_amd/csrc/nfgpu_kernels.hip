@@ -2818,6 +2818,81 @@ __global__ __launch_bounds__(kTPB) void k_find_objects(const FindObjDev* __restr
 }
 
 // ---------------------------------------------------------------------------------
+// Resource calls (nfk_adjust_props): NFCPropertyModule's AddHP / ConsumeHP / EnoughHP / AddMoney /
+// FullHPMP ... (PM:215-472) of a batch.  The host sorts the batch stably by (object, dst), so the
+// calls on one cell are one run of descriptors in call order.  A lane is a call; the lane of a
+// run's first call (len > 0) walks the run with the cell's value in a register — a call reads what
+// the calls before it left — loads each call's bound, and stores the call's result byte and new
+// value at the call's place in the batch.  The other lanes of a run do nothing.  The world's cells
+// are only read: the accepted Sets go through the window's SetProperty queue like any other.
+// No atomics, no LDS, no wave-wide operation, no workgroup waits on another.
+struct AdjDev {
+    uint64_t dst;    // absolute address of the dst cell
+    uint64_t bound;  // absolute address of the bound cell, or 0
+    int64_t v;
+    uint32_t place;  // the call's index in the batch
+    uint32_t len;    // the run's calls for its first call, else 0
+    uint32_t op;     // NFK_ADJ_*
+    uint32_t pad;
+};  // 40 bytes
+static_assert(sizeof(AdjDev) == 40, "AdjDev is 40 bytes");
+// the rule of one call on cur (see nfgpu.h's table): the result byte; *nv the value to Set when bit 1
+// is set.  Add and subtract wrap.
+__host__ __device__ inline uint32_t adj_rule(uint32_t op, int64_t cur, int64_t mx, int64_t v, int64_t* nv) {
+    const int64_t up = (int64_t)((uint64_t)cur + (uint64_t)v), dn = (int64_t)((uint64_t)cur - (uint64_t)v);
+    switch (op) {
+        case 0:  // NFK_ADJ_GAIN_ALIVE
+            if (v <= 0) return 0;
+            if (cur <= 0) return 1;
+            *nv = up > mx ? mx : up;
+            return 3;
+        case 1:  // NFK_ADJ_GAIN_CAP
+            if (v <= 0) return 0;
+            *nv = up > mx ? mx : up;
+            return 3;
+        case 2:  // NFK_ADJ_GAIN
+            if (v <= 0) return 0;
+            *nv = up;
+            return 2;
+        case 3:  // NFK_ADJ_SPEND_ALIVE
+            if (!(cur > 0 && dn >= 0)) return 0;
+            *nv = dn;
+            return 3;
+        case 4:  // NFK_ADJ_SPEND
+            if (v <= 0 || dn < 0) return 0;
+            *nv = dn;
+            return 3;
+        case 5:  // NFK_ADJ_ENOUGH
+            return cur > 0 && dn >= 0 ? 1 : 0;
+        default:  // NFK_ADJ_FILL
+            if (mx <= 0) return 0;
+            *nv = mx;
+            return 3;
+    }
+}
+// n descriptors; the batch has n_batch places (newv / ret hold that many).  A run that would pass the
+// descriptors' end and a place outside the batch are not followed (no store outside the staging
+// buffer); the host fills ret with 0xFF before the launch and takes a place left so for an error.
+__global__ __launch_bounds__(kTPB) void k_adjust(const AdjDev* __restrict__ qs, int32_t n, int32_t n_batch,
+                                                 int64_t* __restrict__ newv, uint8_t* __restrict__ ret) {
+    const int64_t t = (int64_t)blockIdx.x * kTPB + threadIdx.x;
+    if (t >= n) return;  // (nothing wave-wide follows)
+    const uint32_t len = qs[t].len;
+    if (len == 0 || (int64_t)len > n - t) return;
+    int64_t cur = *(const int64_t*)(uintptr_t)qs[t].dst;
+    for (uint32_t k = 0; k < len; k++) {
+        const AdjDev f = qs[t + k];
+        if (f.place >= (uint32_t)n_batch) continue;
+        const int64_t mx = f.bound ? *(const int64_t*)(uintptr_t)f.bound : 0;
+        int64_t nv = cur;
+        const uint32_t r = adj_rule(f.op, cur, mx, f.v, &nv);
+        if (r & 2) cur = nv;
+        newv[f.place] = nv;
+        ret[f.place] = (uint8_t)r;
+    }
+}
+
+// ---------------------------------------------------------------------------------
 // Enter snapshots (nfk_snapshot_objects): what NFCGameServerNet_ServerModule::OnPropertyEnter /
 // OnRecordEnter pack for a batch of (object, view) requests.  The walk is a table (SnapTab, built
 // by the host whenever flags or the walk's order change): the properties by ORDER POSITION (the

@@ -62,11 +62,13 @@ bool linked_property(const void* self, size_t p) {
 
 namespace {
 void drop_views(const void* self);  // (AddObjectEnterCallBack / AddObjectLeaveCallBack's table, below)
+void drop_resource_names(const void* self);  // (SetResourcePropertyNames' table, below)
 }
 
 NFGPUKernelModule::~NFGPUKernelModule() {
     drop_links(this);
     drop_views(this);
+    drop_resource_names(this);
     WaitGather();
     pool_.reset();
     if (world_) nfk_destroy(world_);
@@ -1458,6 +1460,166 @@ double NFGPUKernelModule::GetPropertyFloat(const NFGUID& self, const std::string
     Flush();
     check(nfk_get_props(world_, 1, &self.nHead64, &self.nData64, &pid, &b), "nfk_get_props");
     return dbl_of(b);
+}
+
+// ---- NFCPropertyModule's resource calls (PM:215-472) through nfk_adjust_props ----
+// the eight property names of the named methods, kept beside the modules (the header's layout policy)
+namespace {
+struct ResourceNames {
+    std::string hp = "HP", maxhp = "MAXHP", mp = "MP", maxmp = "MAXMP", sp = "SP", maxsp = "MAXSP", gold = "Gold",
+                money = "Money";
+};
+std::mutex g_res_mu;
+std::unordered_map<const void*, ResourceNames> g_res_names;
+std::atomic<int> g_res_modules{0};
+ResourceNames resource_names(const void* self) {
+    if (!g_res_modules.load(std::memory_order_acquire)) return ResourceNames{};
+    std::lock_guard<std::mutex> lk(g_res_mu);
+    auto it = g_res_names.find(self);
+    return it == g_res_names.end() ? ResourceNames{} : it->second;
+}
+void drop_resource_names(const void* self) {
+    if (!g_res_modules.load(std::memory_order_acquire)) return;
+    std::lock_guard<std::mutex> lk(g_res_mu);
+    if (g_res_names.erase(self)) g_res_modules.fetch_sub(1, std::memory_order_release);
+}
+}  // namespace
+
+void NFGPUKernelModule::SetResourcePropertyNames(const std::string& hp, const std::string& maxhp, const std::string& mp,
+                                                 const std::string& maxmp, const std::string& sp, const std::string& maxsp,
+                                                 const std::string& gold, const std::string& money) {
+    if (committed_) throw std::runtime_error("SetResourcePropertyNames after AfterInit");
+    std::lock_guard<std::mutex> lk(g_res_mu);
+    if (g_res_names.count(this)) throw std::runtime_error("SetResourcePropertyNames: the names are set once");
+    g_res_names[this] = ResourceNames{hp, maxhp, mp, maxmp, sp, maxsp, gold, money};
+    g_res_modules.fetch_add(1, std::memory_order_release);
+}
+
+bool NFGPUKernelModule::AdjustProperties(int n, const NFGUID* guids, const uint8_t* op, const std::string* dst,
+                                         const std::string* bound, const int64_t* value, uint8_t* ret) {
+    using Fn = int (*)(void*, int32_t, const int64_t*, const int64_t*, const uint8_t*, const int32_t*, const int32_t*,
+                       const int64_t*, uint8_t*);
+    static const Fn fn = (Fn)nfgpu_symbol("nfk_adjust_props");  // (looked up at first use, as nfk_swap_rows)
+    if (!fn) throw std::runtime_error("nfk_adjust_props: the nfgpu library has no such entry point");
+    if (!committed_ || n < 0) return false;
+    // the names resolved once per distinct name (a batch usually holds a handful)
+    std::unordered_map<std::string, int32_t> pid_of;
+    auto resolve = [&](const std::string& name, int32_t* pid) {
+        auto it = pid_of.find(name);
+        if (it == pid_of.end()) {
+            const int p = prop_ix_.find(name);
+            const int32_t d = p < 0 || props_[(size_t)p].type != TDATA_INT ? -1 : dev_pid_[(size_t)p];
+            it = pid_of.emplace(name, d).first;
+        }
+        *pid = it->second;
+        return *pid >= 0;
+    };
+    std::vector<int64_t> gh, gd, v;
+    std::vector<uint8_t> o;
+    std::vector<int32_t> pd, pb, at;
+    for (int i = 0; i < n; i++) {
+        int32_t d = -1, b = -1;
+        const bool takes = op[i] == NFK_ADJ_GAIN_ALIVE || op[i] == NFK_ADJ_GAIN_CAP || op[i] == NFK_ADJ_FILL;
+        if (op[i] > NFK_ADJ_FILL || !resolve(dst[i], &d) || takes != !bound[i].empty() || (takes && !resolve(bound[i], &b)))
+            return false;
+        if (linked_property(this, (size_t)prop_ix_.find(dst[i]))) return false;
+        if (ObjectIndex(guids[i]) < 0) {  // GetPropertyInt gives 0 there and the Set is dropped (KM:331, KM:411)
+            ret[i] = op[i] <= NFK_ADJ_GAIN_CAP && value[i] > 0 ? NFK_ADJ_RET : 0;
+            continue;
+        }
+        gh.push_back(guids[i].nHead64);
+        gd.push_back(guids[i].nData64);
+        o.push_back(op[i]);
+        pd.push_back(d);
+        pb.push_back(b);
+        v.push_back(value[i]);
+        at.push_back(i);
+    }
+    if (at.empty()) return true;
+    Flush();  // (the buffered Set calls first: the calls see them)
+    std::vector<uint8_t> r(at.size());
+    check(fn(world_, (int32_t)at.size(), gh.data(), gd.data(), o.data(), pd.data(), pb.data(), v.data(), r.data()),
+          "nfk_adjust_props");
+    for (size_t k = 0; k < at.size(); k++) {
+        ret[at[k]] = r[k];
+        if (!(r[k] & NFK_ADJ_SET)) continue;
+        const NFGUID& g = guids[at[k]];
+        if (walk_reads_ && in_walk_) WalkWrote(g, pd[k]);
+        if (shard_) NoteCall(g);
+        pending_calls_++;
+    }
+    return true;
+}
+
+// one named call: the reference's bool
+static bool resource_call(NFGPUKernelModule* m, const NFGUID& self, uint8_t op, const std::string& dst,
+                          const std::string& bound, int64_t v) {
+    uint8_t r = 0;
+    if (!m->AdjustProperties(1, &self, &op, &dst, &bound, &v, &r)) return false;
+    return (r & NFK_ADJ_RET) != 0;
+}
+
+bool NFGPUKernelModule::FullHPMP(const NFGUID& self) {
+    const ResourceNames nm = resource_names(this);
+    const NFGUID g[2] = {self, self};
+    const uint8_t op[2] = {NFK_ADJ_FILL, NFK_ADJ_FILL};
+    const std::string d[2] = {nm.hp, nm.mp}, b[2] = {nm.maxhp, nm.maxmp};
+    const int64_t v[2] = {0, 0};
+    uint8_t r[2];
+    AdjustProperties(2, g, op, d, b, v, r);
+    return true;  // PM:229
+}
+bool NFGPUKernelModule::FullSP(const NFGUID& self) {
+    const ResourceNames nm = resource_names(this);
+    return resource_call(this, self, NFK_ADJ_FILL, nm.sp, nm.maxsp, 0);
+}
+bool NFGPUKernelModule::AddHP(const NFGUID& self, int64_t nValue) {
+    const ResourceNames nm = resource_names(this);
+    return resource_call(this, self, NFK_ADJ_GAIN_ALIVE, nm.hp, nm.maxhp, nValue);
+}
+bool NFGPUKernelModule::ConsumeHP(const NFGUID& self, int64_t nValue) {
+    return resource_call(this, self, NFK_ADJ_SPEND_ALIVE, resource_names(this).hp, "", nValue);
+}
+bool NFGPUKernelModule::EnoughHP(const NFGUID& self, int64_t nValue) {
+    return resource_call(this, self, NFK_ADJ_ENOUGH, resource_names(this).hp, "", nValue);
+}
+bool NFGPUKernelModule::AddMP(const NFGUID& self, int64_t nValue) {
+    const ResourceNames nm = resource_names(this);
+    return resource_call(this, self, NFK_ADJ_GAIN_CAP, nm.mp, nm.maxmp, nValue);
+}
+bool NFGPUKernelModule::ConsumeMP(const NFGUID& self, int64_t nValue) {
+    return resource_call(this, self, NFK_ADJ_SPEND_ALIVE, resource_names(this).mp, "", nValue);
+}
+bool NFGPUKernelModule::EnoughMP(const NFGUID& self, int64_t nValue) {
+    return resource_call(this, self, NFK_ADJ_ENOUGH, resource_names(this).mp, "", nValue);
+}
+bool NFGPUKernelModule::AddSP(const NFGUID& self, int64_t nValue) {
+    const ResourceNames nm = resource_names(this);
+    return resource_call(this, self, NFK_ADJ_GAIN_CAP, nm.sp, nm.maxsp, nValue);
+}
+bool NFGPUKernelModule::ConsumeSP(const NFGUID& self, int64_t nValue) {
+    return resource_call(this, self, NFK_ADJ_SPEND_ALIVE, resource_names(this).sp, "", nValue);
+}
+bool NFGPUKernelModule::EnoughSP(const NFGUID& self, int64_t nValue) {
+    return resource_call(this, self, NFK_ADJ_ENOUGH, resource_names(this).sp, "", nValue);
+}
+bool NFGPUKernelModule::AddMoney(const NFGUID& self, int64_t nValue) {
+    return resource_call(this, self, NFK_ADJ_GAIN, resource_names(this).gold, "", nValue);
+}
+bool NFGPUKernelModule::ConsumeMoney(const NFGUID& self, int64_t nValue) {
+    return resource_call(this, self, NFK_ADJ_SPEND, resource_names(this).gold, "", nValue);
+}
+bool NFGPUKernelModule::EnoughMoney(const NFGUID& self, int64_t nValue) {
+    return resource_call(this, self, NFK_ADJ_ENOUGH, resource_names(this).gold, "", nValue);
+}
+bool NFGPUKernelModule::AddDiamond(const NFGUID& self, int64_t nValue) {
+    return resource_call(this, self, NFK_ADJ_GAIN, resource_names(this).money, "", nValue);
+}
+bool NFGPUKernelModule::ConsumeDiamond(const NFGUID& self, int64_t nValue) {
+    return resource_call(this, self, NFK_ADJ_SPEND, resource_names(this).money, "", nValue);
+}
+bool NFGPUKernelModule::EnoughDiamond(const NFGUID& self, int64_t nValue) {
+    return resource_call(this, self, NFK_ADJ_ENOUGH, resource_names(this).money, "", nValue);
 }
 
 bool NFGPUKernelModule::SetPropertyObject(const NFGUID& self, const std::string& name, const NFGUID& v) {

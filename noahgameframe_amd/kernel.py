@@ -56,6 +56,12 @@ class Outputs(ctypes.Structure):
                   "msg_rcpt", "slot_obj", "ev_old_h", "ev_new_h", "re_old_h", "re_new_h"]])
 
 
+class AdjustStats(ctypes.Structure):
+    """nfk_adjust_stats_t"""
+    _fields_ = [("kernel_ms", ctypes.c_double), ("bytes", ctypes.c_int64), ("n_dev", ctypes.c_int32),
+                ("n_host", ctypes.c_int32), ("n_set", ctypes.c_int32), ("pad", ctypes.c_int32)]
+
+
 class Query(ctypes.Structure):
     """nfk_query (include/nfgpu.h): one scene query of a nfk_query_objects batch."""
     _fields_ = [("scene", ctypes.c_int32), ("group", ctypes.c_int32), ("flags", ctypes.c_uint32),
@@ -102,6 +108,9 @@ LINK_SUM32 = 0    # NFK_LINK_SUM32 (nfk_link_record's mode)
 Q_PLAYERS, Q_OTHERS = 0, 1
 Q_ALL_GROUPS = 1
 Q_INT_EQ32, Q_OBJ_EQ = 0, 1
+# nfk_adjust_props' ops (NFK_ADJ_*) and result bits
+ADJ_GAIN_ALIVE, ADJ_GAIN_CAP, ADJ_GAIN, ADJ_SPEND_ALIVE, ADJ_SPEND, ADJ_ENOUGH, ADJ_FILL = range(7)
+ADJ_RET, ADJ_SET = 1, 2
 
 
 def query(scene, group=None, who=Q_PLAYERS, cls_mask=0x7FFF, pid=-1, mode=Q_INT_EQ32, value=0, value_head=0,
@@ -171,6 +180,8 @@ def load_library(path=LIB_PATH):
         "nfk_swap_rows": [VP, I32, VP, VP, VP, VP, VP],
         "nfk_link_record": [VP, I32, I32, VP, I32],
         "nfk_view_changes": [VP, P(ViewChanges)],
+        "nfk_adjust_props": [VP, I32, VP, VP, VP, VP, VP, VP, VP],
+        "nfk_adjust_props_obj": [VP, I32, VP, VP, VP, VP, VP, VP], "nfk_adjust_stats": [VP, P(AdjustStats)],
     }
     for name, args in sig.items():
         if not hasattr(lib, name) and os.environ.get("NFGPU_LIB"):
@@ -880,6 +891,37 @@ class NFKernelModule:
         out = np.zeros(len(a[0]), np.uint64)
         self._chk(self.lib.nfk_get_props(self.h, len(a[0]), *[_p(x) for x in a], _p(out)))
         return out
+
+    # ---- NFCPropertyModule's resource calls (PM:215-472): AddHP / ConsumeHP / EnoughHP / AddMoney / FullHPMP ... ----
+    def adjust_props(self, guid_head, guid_data, op, dst, bound, value, stats=None):
+        """nfk_adjust_props: n (object, ADJ_* op, dst, bound or -1, int64 value) calls applied in array
+        order as the loop get_props / the op's rule / set_props would -> uint8 results (ADJ_RET: the
+        reference's return value, ADJ_SET: a Set was queued).  stats: a dict that receives the
+        launch's device time (kernel_ms, with set_profiling(True)), the bytes read back, the calls
+        answered by the kernel (n_dev) and on the host (n_host) and the Sets queued (n_set)."""
+        a = [np.ascontiguousarray(x, t) for x, t in
+             ((guid_head, np.int64), (guid_data, np.int64), (op, np.uint8), (dst, np.int32), (bound, np.int32),
+              (value, np.int64))]
+        out = np.zeros(len(a[0]), np.uint8)
+        self._chk(self.lib.nfk_adjust_props(self.h, len(a[0]), *[_p(x) for x in a], _p(out)))
+        self._adjust_stats(stats)
+        return out
+
+    def adjust_props_obj(self, obj, op, dst, bound, value, stats=None):
+        """nfk_adjust_props_obj: adjust_props by object index (query_objects' hits, the outputs' ev_obj)"""
+        a = [np.ascontiguousarray(x, t) for x, t in
+             ((obj, np.int32), (op, np.uint8), (dst, np.int32), (bound, np.int32), (value, np.int64))]
+        out = np.zeros(len(a[0]), np.uint8)
+        self._chk(self.lib.nfk_adjust_props_obj(self.h, len(a[0]), *[_p(x) for x in a], _p(out)))
+        self._adjust_stats(stats)
+        return out
+
+    def _adjust_stats(self, stats):
+        if stats is None:
+            return
+        st = AdjustStats()
+        self._chk(self.lib.nfk_adjust_stats(self.h, ctypes.byref(st)))
+        stats.update(kernel_ms=st.kernel_ms, bytes=st.bytes, n_dev=st.n_dev, n_host=st.n_host, n_set=st.n_set)
 
     def GetPropertyInt(self, guid, prop):
         pid = wl.PID[prop] if isinstance(prop, str) else prop
